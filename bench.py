@@ -6,9 +6,12 @@ TFJob Worker=N on MI355X (BASELINE.json config #3, metric "samples/sec
     python bench.py --gpus N --steps K --warmup W          # through the operator
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   # one rank per GPU
     python bench.py --direct ...                            # no operator (profilers)
+    python bench.py --full ...          # + latency probes, calibration, RCCL record, collectives A/B
+    python bench.py --dump-outputs DIR ...   # the last timed step's loss and parameters as DIR/*.npy
 
 Rank 0 prints ONE JSON line: ``value`` = whole-job samples/sec (sequences of
-``seq_len`` tokens), MAX step time over ranks, plus ``submit_to_first_step_p50_s``.
+``seq_len`` tokens), MAX step time over ranks (``ms_per_step``); with ``--full``
+also ``submit_to_first_step_p50_s`` over the latency probes.
 Implementation: :mod:`tf_operator_amd.bench.flagship`.
 """
 from __future__ import annotations

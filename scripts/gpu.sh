@@ -10,7 +10,7 @@
 #   tests            pytest -m gpu (one process, per-test timeout)
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (through the operator, N=1, driver defaults)
+#   bench            python bench.py --full (through the operator, N=1; latency probes and calibration included)
 #   bench:<args>     python bench.py <args, comma separated>
 #   direct:<args>    python bench.py --direct <args> (no operator)
 #   prof             rocprofv3 --kernel-trace --stats of bench.py --direct (2 timed steps)
@@ -40,7 +40,7 @@ for st in "$@"; do
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread || exit $? ;;
     tests:*) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${st#tests:}" || exit $? ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 900 python bench.py || exit $? ;;
+    bench) run bench 900 python bench.py --full || exit $? ;;
     bench:*) IFS=, read -ra A <<< "${st#bench:}"; run bench 1100 python bench.py "${A[@]}" || exit $? ;;
     direct:*) IFS=, read -ra A <<< "${st#direct:}"; run direct 900 python bench.py --direct "${A[@]}" || exit $? ;;
     prof)

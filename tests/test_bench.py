@@ -14,7 +14,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TINY = ["--model", "llama-tiny", "--seq-len", "64", "--micro-batch", "2", "--steps", "3", "--warmup", "1"]
+# --full: the latency probes and the collectives A/B record are not part of a plain run
+TINY = ["--model", "llama-tiny", "--seq-len", "64", "--micro-batch", "2", "--steps", "3", "--warmup", "1", "--full"]
 
 
 def _port():
@@ -184,3 +185,49 @@ def test_bench_launcher_eight_workers():
     _check(r, 8)
     assert r["config"]["launched_by"] == "operator"
     assert len(r["submit_to_first_step"]["samples_s"]) == 1   # the benchmark job itself
+
+
+def test_full_only_options_need_full():
+    """A plain run is the timed steps alone: every extra is off, asking for one
+    without --full is an error, and --full restores each default."""
+    from tf_operator_amd.bench import flagship
+
+    ap = flagship.parser()
+    plain = flagship.resolve_full(ap.parse_args(["--latency-probes", "0"]))
+    assert (plain.latency_probes, plain.cold_probes, plain.calibrate, plain.collectives_ab, plain.rccl_log) == (
+        0, 0, "0", "0", "0")
+    full = flagship.resolve_full(ap.parse_args(["--full", "--cold-probes", "1"]))
+    assert (full.latency_probes, full.cold_probes, full.calibrate, full.collectives_ab, full.rccl_log) == (
+        3, 1, "1", "auto", "auto")
+    for extra in (["--latency-probes", "1"], ["--cold-probes", "1"], ["--calibrate", "1"], ["--collectives-ab", "auto"],
+                  ["--rccl-log", "1"]):
+        with pytest.raises(ValueError, match="needs --full"):
+            flagship.resolve_full(ap.parse_args(extra))
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run carries no probe / calibration records, --steps sets the
+    timed steps, and --dump-outputs writes the last step's loss and parameters
+    as float32 .npy files that a second run with the same arguments repeats
+    bit for bit."""
+    import numpy as np
+
+    got = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, "bench.py", "--direct", "--gpus", "1", "--model", "llama-tiny", "--seq-len",
+                            "64", "--micro-batch", "2", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                            str(tmp_path / d)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=280)
+        assert p.returncode == 0, p.stderr[-4000:]
+        r = _json_line(p.stdout)
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0
+        assert abs(r["value"] - 2 / (r["ms_per_step"] / 1000)) / r["value"] < 0.01
+        assert "calibration" not in r and "rccl" not in r and "submit_to_first_step" not in r
+        assert sorted(os.listdir(tmp_path / d)) == ["loss.npy", "params.npy"]
+        arrs = {n: np.load(tmp_path / d / f"{n}.npy") for n in ("loss", "params")}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert r["dumped_outputs"]["arrays"] == {n: list(a.shape) for n, a in arrs.items()}
+        assert arrs["loss"].shape == (1,) and abs(float(arrs["loss"][0]) - r["loss"]) < 1e-3
+        assert arrs["params"].size > 1000 and np.isfinite(arrs["params"]).all()
+        got.append(arrs)
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in got[0])

@@ -20,7 +20,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = ["--model", "llama-tiny", "--seq-len", "128", "--micro-batch", "2", "--steps", "3", "--warmup", "1",
         "--latency-probes", "0", "--cold-probes", "0", "--calibrate", "0", "--zero", "1", "--collectives-ab", "1",
-        "--ab-steps", "2"]
+        "--ab-steps", "2", "--full"]   # the A/B is not part of a plain run
 
 
 def _port():

@@ -8,13 +8,13 @@ Three ways in, one measurement:
   the whole operator stack runs in this process -- fake API server, the
   operator (C++ reconcile core), local kubelet with node-visible devices --
   and the benchmark is SUBMITTED as a ``TFJob`` with ``Worker=N`` whose
-  replicas run :func:`run_replica`.  Before it, ``--latency-probes`` TFJobs
+  replicas run :func:`run_replica`.  Before it, under ``--full``, ``--latency-probes`` TFJobs
   running the user-facing ``examples/llama_train`` payload for one step are
   submitted and timed from ``create()`` to rank 0's first completed
   optimizer step (reported back to the operator).  This process never
   touches the GPU.
 * **torchrun** (the driver's N > 1 launch: ``WORLD_SIZE`` set by the
-  elastic agent): every rank runs :func:`run_replica` directly.  Before any
+  elastic agent): every rank runs :func:`run_replica` directly.  Under ``--full``, before any
   rank touches a GPU, rank 0 runs the same latency probes (TFJob Worker=N
   through a local operator stack) while the other ranks wait on the agent's
   store.
@@ -26,6 +26,12 @@ barrier + ``torch.cuda.synchronize()`` on both sides, MAX over ranks; full
 forward + backward + gradient reduce-scatter/all-reduce + AdamW.  Rank 0
 builds the one JSON line; ``n_gpus`` is the size of the initialised RCCL
 process group, and the run fails when it differs from ``--gpus``.
+
+A plain run does only that: set up, warm up, time the K steps, write the
+last step's outputs when ``--dump-outputs DIR`` is given, print the line.
+Everything else the benchmark measures -- the latency probes (warm and
+cold), the box-speed calibration GEMMs and clock sampling, RCCL's transport
+record and the collectives A/B -- runs under ``--full`` only.
 
 Reference: the metric's 8-worker job is
 ``examples/v1/distribution_strategy/keras-API/multi_worker_strategy-with-keras.py:76-77``
@@ -60,11 +66,20 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--bucket-mb", type=float, default=None)
     ap.add_argument("--zero", choices=("auto", "0", "1"), default="auto",
                     help="sharded optimizer (reduce-scatter / owned-shard AdamW / all-gather); auto = on for N > 1")
-    ap.add_argument("--latency-probes", type=int, default=3,
-                    help="TFJobs submitted (and timed submit -> first step) before the throughput run; 0 = skip")
-    ap.add_argument("--cold-probes", type=int, default=2,
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the submit -> first-step latency "
+                         "probes, the box-speed calibration, RCCL's transport record and the collectives A/B "
+                         "(each with its own option below; without --full they are all off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float32): the loss, and a fixed seeded sample of the updated parameters and of the "
+                         "gradients")
+    ap.add_argument("--latency-probes", type=int, default=None,
+                    help="TFJobs submitted (and timed submit -> first step) before the throughput run; 0 = skip "
+                         "(--full: default 3)")
+    ap.add_argument("--cold-probes", type=int, default=None,
                     help="extra probe TFJobs whose replicas start as cold processes (a real kubelet's start), "
-                         "reported as submit_to_first_step_cold_p50_s; 0 = skip")
+                         "reported as submit_to_first_step_cold_p50_s; 0 = skip (--full: default 2)")
     ap.add_argument("--probe-timeout", type=float, default=180.0, help="per probe job (s)")
     ap.add_argument("--warm-start", choices=("0", "1"), default="1",
                     help="replicas start as forks of the local kubelet's warm interpreter (torch pre-imported, "
@@ -72,16 +87,41 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--direct", action="store_true",
                     help="run the replica in this process (no operator; for profilers)")
     ap.add_argument("--result-file", default=None, help=argparse.SUPPRESS)  # replica -> launcher
-    ap.add_argument("--rccl-log", choices=("auto", "0", "1"), default="auto",
-                    help="capture RCCL's transport selection (NCCL_DEBUG=INFO to a file) into the JSON line")
-    ap.add_argument("--calibrate", choices=("0", "1"), default="1",
-                    help="box-speed record: fixed-shape GEMM rates around the timed region, clock during it")
-    ap.add_argument("--collectives-ab", choices=("auto", "0", "1"), default="auto",
+    ap.add_argument("--rccl-log", choices=("auto", "0", "1"), default=None,
+                    help="capture RCCL's transport selection (NCCL_DEBUG=INFO to a file) into the JSON line "
+                         "(--full: default auto)")
+    ap.add_argument("--calibrate", choices=("0", "1"), default=None,
+                    help="box-speed record: fixed-shape GEMM rates around the timed region, clock during it "
+                         "(--full: default 1)")
+    ap.add_argument("--collectives-ab", choices=("auto", "0", "1"), default=None,
                     help="after the timed region, time the ZeRO-1 collectives on RCCL and on the copy engines "
                          "(copy-engine pulls) in alternating windows of the same process group; auto = on for "
-                         "a sharded one-node GPU job with N > 1")
+                         "a sharded one-node GPU job with N > 1 (--full: default auto)")
     ap.add_argument("--ab-steps", type=int, default=3, help="timed steps per collectives A/B window")
     return ap
+
+
+# what only a --full run does: option -> (its default under --full, its "off" value)
+FULL_ONLY = {"latency_probes": (3, 0), "cold_probes": (2, 0), "rccl_log": ("auto", "0"), "calibrate": ("1", "0"),
+             "collectives_ab": ("auto", "0")}
+
+
+def resolve_full(args, ap: argparse.ArgumentParser | None = None):
+    """A plain run measures the headline figure and nothing else: every
+    FULL_ONLY option is off, and asking for one without --full is an error
+    (not a silently smaller run).  Under --full each takes its default."""
+    for name, (dflt, off) in FULL_ONLY.items():
+        v = getattr(args, name)
+        if args.full:
+            setattr(args, name, dflt if v is None else v)
+        elif v is not None and v != off:
+            msg = f"--{name.replace('_', '-')} {v} needs --full"
+            if ap is None:
+                raise ValueError(msg)
+            ap.error(msg)
+        else:
+            setattr(args, name, off)
+    return args
 
 
 def mode() -> str:
@@ -91,7 +131,10 @@ def mode() -> str:
 
 
 def main(argv=None, t_proc_start=None) -> int:
-    args = parser().parse_args(argv)
+    ap = parser()
+    args = resolve_full(ap.parse_args(argv), ap)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     t_proc_start = t_proc_start or time.time()
     m = "replica" if args.direct else mode()
     if m == "launcher":
@@ -497,6 +540,30 @@ def collectives_ab(tr, batches, args, info, rccl_ok) -> dict:
     return out
 
 
+DUMP_SAMPLE = 8 << 20   # parameters sampled by --dump-outputs: 32 MiB of float32
+
+
+def dump_outputs(path: str, tr, loss) -> dict:
+    """What the last timed step handed its caller, as float32 ``.npy`` files
+    under `path`: ``loss`` (the step's return value) and ``params`` (the flat
+    parameter buffer after the update; above DUMP_SAMPLE elements a fixed,
+    seeded sample of its positions, in ascending order).  Returns
+    {name: shape}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    p = tr.flat.param.detach()
+    if p.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240229).integers(0, p.numel(), DUMP_SAMPLE, dtype=np.int64))
+        p = p.index_select(0, torch.from_numpy(idx).to(p.device))
+    arrays = {"loss": np.asarray([float(loss)], dtype=np.float32),
+              "params": p.float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _ab_watchdog(budget_s: float, emit, code: int = 0):
     """A hung A/B window (a stalled copy-engine pull, a collective that never
     completes) or teardown must not cost the headline line: after `budget_s`
@@ -603,6 +670,7 @@ def run_replica(args, t_proc_start: float, probe: dict | None = None, launched_b
     # (one fp64 reduction over the flat bf16 buffer, outside the timed region)
     if tr.gather is not None:
         tr.gather.wait_all()
+    dumped = dump_outputs(args.dump_outputs, tr, loss) if args.dump_outputs and info.rank == 0 else None
     csum = float(tr.flat.param.sum(dtype=torch.float64))  # no fp32 copy of 16 GB of weights
     in_sync = tdist.all_max(csum, dev) == -tdist.all_max(-csum, dev)
     loss_max = tdist.all_max(loss_v, dev)
@@ -666,6 +734,8 @@ def run_replica(args, t_proc_start: float, probe: dict | None = None, launched_b
             # GEMMs that left the hand-written kernels for the library (ops/gemm.py): 0 at the bench shape
             "gemm_fallbacks": {"calls": sum(_gemm.fallbacks().values()), "by_shape": _gemm.fallbacks()},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         cr = cal.record()
         if cr is not None:
             out["calibration"] = cr
@@ -779,6 +849,10 @@ def run_launcher(args) -> int:
                "--calibrate", args.calibrate, "--collectives-ab", args.collectives_ab, "--ab-steps", str(args.ab_steps)]
         if args.bucket_mb is not None:
             cmd += ["--bucket-mb", str(args.bucket_mb)]
+        if args.full:
+            cmd += ["--full"]
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", args.dump_outputs]
         timeout = args.probe_timeout + 60 + 30 * (args.steps + args.warmup)
         try:
             job = _run_job(c, "bench", n, cmd, timeout, env={"TOA_BENCH_RCCL_DIR": res_dir, "PYTHONUNBUFFERED": "1"})

@@ -1146,8 +1146,9 @@ def epilogue_delta(a: Asm):
 
 def epilogue_resadd(a: Asm):
     """C = X W^T + R (bf16 R laid out like C, kernarg S): the residual add of
-    the attention output projection in its epilogue, so the RMSNorm after it
-    reads one tensor and writes one (ops/llm._AttnOutProj).  R row blocks
+    the attention output and MLP down projections in their epilogue, so the
+    RMSNorm after it reads one tensor and writes one (ops/gemm.linear_resadd,
+    called by ops/llm.attention_block and swiglu_mlp).  R row blocks
     load DELTA_DEPTH blocks ahead (counted vmcnt); the sum is rounded to bf16
     once, as the unfused add of the bf16 GEMM output and R is not (the fused
     path adds in fp32 before the one rounding)."""

@@ -895,12 +895,12 @@ def test_first_step_gemms_run_on_the_assembly_kernel():
         direct = torch.empty(512, 768, device=DEV, dtype=torch.bfloat16)
         L.call("toa_gemm_asm", L.ptr(x), 384, L.ptr(w), 384, L.ptr(direct), 768, 512, 768, 384, L.stream(x))
         with gemm.first_step(True):
-            assert gemm._asm_shape_ok(x, w)
+            assert gemm.asm_takes(x, w)
             y = gemm.linear_fwd(x, w)
             xo = torch.randn(100, 384, device=DEV, dtype=torch.bfloat16)  # not a 256-row multiple: the library
-            assert not gemm._asm_shape_ok(xo, w)
+            assert not gemm.asm_takes(xo, w)
             yo = gemm.linear_fwd(xo, w)
-        assert not gemm._asm_shape_ok(x, w)  # outside the scope: the policy's library path
+        assert not gemm.asm_takes(x, w)  # outside the scope: the policy's library path
         torch.cuda.synchronize()
         assert torch.equal(y, direct)
         assert rel(y, x.float() @ w.float().t()) < 1e-2
@@ -1590,14 +1590,14 @@ def test_attn_out_proj_delta_rows(monkeypatch):
         wo.main_grad = torch.zeros_like(wo)
         wo._toa_wt = wo.data.t().contiguous()
         dy = torch.randn(B * S, H * D, device=DEV).to(torch.bfloat16)
-        llm.attn_out_proj(o, wo, B, S, H).backward(dy)
+        link = llm._DeltaLink()
+        llm.attn_out_proj(o, wo, B, S, H, link=link).backward(dy)
         torch.cuda.synchronize()
-        pend = llm._PENDING_DELTA
-        llm._PENDING_DELTA = None
-        assert pend is not None and pend[0] == o.grad.data_ptr()
+        assert link.ndelta is not None and link.do_ptr == o.grad.data_ptr() and link.numel == o.grad.numel()
         assert torch.equal(o.grad, gemm.linear_dgrad(dy, wo))
         ref = -(o.grad.float() * o.detach().float()).view(B, S, H, D).sum(-1).permute(0, 2, 1).reshape(-1)
-        assert rel(pend[2], ref) < 1e-4
+        assert rel(link.ndelta, ref) < 1e-4
+        assert link.take(o.grad) is not None and link.ndelta is None   # taken once, then empty
     finally:
         gemm.set_mode(old)
     losses = {}
@@ -1606,7 +1606,6 @@ def test_attn_out_proj_delta_rows(monkeypatch):
         tr = LlamaTrainer(PRESETS["llama-tiny128"], torch.device(DEV), micro_batch=2, seq_len=512, seed=0)
         b = tr.synthetic_batch()
         losses[fused] = [float(tr.step([b])) for _ in range(3)]
-        assert llm._PENDING_DELTA is None
     for a, c in zip(losses["1"], losses["0"]):
         assert abs(a - c) <= 1e-3 * abs(c), losses
 
@@ -1630,7 +1629,7 @@ def test_resadd_epilogue_and_presummed_norm(monkeypatch):
         wo = (torch.randn(Hd, Hd, device=DEV) / Hd ** 0.5).to(torch.bfloat16)
         h = torch.randn(T, Hd, device=DEV).to(torch.bfloat16)
         assert llm.attn_out_proj_resadd_ok(o, wo, h)
-        out = llm._AttnOutProj.apply(o, wo, 2, 512, 4, h)
+        out = llm._AttnOutProj.apply(o, wo, 2, 512, 4, h, None)
         ref = o.float() @ wo.float().t() + h.float()
         assert rel(out, ref) < 1e-2
     finally:

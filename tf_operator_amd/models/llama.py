@@ -26,10 +26,8 @@ import torch
 
 from ..ops.embedding import Embedding
 from ..ops.linear import linear
-from ..ops.llm import (attn_out_proj, attn_out_proj_resadd_ok, causal_attention, cross_entropy, qkv_rope_attention,
-                       qkv_rope_attention_ok, rope_attention, rope_qkv, rope_tables, swiglu_mlp,
-                       swiglu_mlp_resadd_ok)
-from ..ops.norm import RMSNorm, add_rms_norm
+from ..ops.llm import (attention_block, cross_entropy, rope_cossin, rope_tables, swiglu_mlp, swiglu_mlp_resadd_ok)
+from ..ops.norm import RMSNorm
 
 
 @dataclasses.dataclass
@@ -97,7 +95,7 @@ class LlamaBlock(torch.nn.Module):
     def params_backward_order(self):
         return [self.wd, self.wgu, self.mlp_norm.weight, self.wo, self.wqkv, self.attn_norm.weight]
 
-    def forward(self, h, delta, cos, sin, B, S):
+    def forward(self, h, delta, cos, sin, B, S, cossin=None):
         cfg = self.cfg
         if delta is None:
             x = self.attn_norm(h)
@@ -105,34 +103,14 @@ class LlamaBlock(torch.nn.Module):
             h, x = self.attn_norm.presummed(h)
         else:
             h, x = self.attn_norm(h, delta)
-        if cfg.kv_layout in ("packed", "auto") and qkv_rope_attention_ok(x, self.wqkv, S, cfg.heads, cfg.kv_heads,
-                                                                         cfg.head_dim):
-            # the projection's GEMM writes rotated head-major q | k | v (no qkv tensor, no RoPE pass)
-            o = qkv_rope_attention(x, self.wqkv, cos, sin, B, S, cfg.heads, cfg.kv_heads, cfg.head_dim)
-        elif cfg.kv_layout in ("packed", "auto"):
-            # the attention kernel reads packed GQA K/V natively; RoPE and
-            # attention are one autograd node whose backward writes d(qkv)
-            qkv = linear(x, self.wqkv)
-            o = rope_attention(qkv, cos, sin, B, S, cfg.heads, cfg.kv_heads, cfg.head_dim)  # [B, S, H, D]
-        else:
-            qkv = linear(x, self.wqkv)
-            rep = cfg.heads // cfg.kv_heads
-            q, k, v = rope_qkv(qkv, cos, sin, B, S, cfg.heads, cfg.kv_heads, cfg.head_dim, rep)
-            o = causal_attention(q, k, v, out_layout="bshd")  # [B, S, H, D]: no transpose copy
-        o = o.reshape(B * S, cfg.heads * cfg.head_dim)
-        # the RoPE-attention nodes consume the delta rows the projection's backward leaves; the other
-        # attention path does not, so it keeps the plain linear
-        packed = cfg.kv_layout in ("packed", "auto")
-        if o.is_cuda and packed and attn_out_proj_resadd_ok(o, self.wo, h):
-            # the residual add in the projection's epilogue; the norm then reads the sum once
-            h, x = self.mlp_norm.presummed(attn_out_proj(o, self.wo, B, S, cfg.heads, residual=h))
-        else:
-            a = attn_out_proj(o, self.wo, B, S, cfg.heads) if (o.is_cuda and packed) else linear(o, self.wo)
-            h, x = self.mlp_norm(h, a)
+        a, summed = attention_block(x, self.wqkv, self.wo, cos, sin, B, S, cfg.heads, cfg.kv_heads, cfg.head_dim,
+                                    residual=h, kv_layout=cfg.kv_layout, cossin=cossin)
+        # summed: the output projection's epilogue added the residual; the norm then reads the sum once
+        h, x = self.mlp_norm.presummed(a) if summed else self.mlp_norm(h, a)
         if swiglu_mlp_resadd_ok(x, self.wd, h):
             # + the residual in the down projection's epilogue: the next norm reads the sum once
             return swiglu_mlp(x, self.wgu, self.wd, residual=h), PRESUMMED
-        delta = swiglu_mlp(x, self.wgu, self.wd)  # SwiGLU fused into the GEMMs under TOA_GEMM=hip
+        delta = swiglu_mlp(x, self.wgu, self.wd)  # SwiGLU in the GEMMs' epilogues under the asm GEMM policy
         return h, delta
 
 
@@ -178,18 +156,22 @@ class Llama(torch.nn.Module):
         return p.dim() == 1
 
     def rope(self, S, device):
+        """(cos, sin [S, D/2], cos | sin stacked [2, S, D/2]) fp32 of this
+        model's rope_theta, built once per (S, device): the stacked copy is
+        the table the fused QKV + RoPE GEMM reads."""
         key = (S, str(device))
         if key not in self._rope_cache:
-            self._rope_cache[key] = rope_tables(S, self.cfg.head_dim, self.cfg.rope_theta, device=device)
+            cos, sin = rope_tables(S, self.cfg.head_dim, self.cfg.rope_theta, device=device)
+            self._rope_cache[key] = (cos, sin, rope_cossin(cos, sin))
         return self._rope_cache[key]
 
     def forward(self, tokens, targets=None):
         B, S = tokens.shape
-        cos, sin = self.rope(S, tokens.device)
+        cos, sin, cossin = self.rope(S, tokens.device)
         h = self.embed(tokens).view(B * S, self.cfg.hidden)
         delta = None
         for blk in self.blocks:
-            h, delta = blk(h, delta, cos, sin, B, S)
+            h, delta = blk(h, delta, cos, sin, B, S, cossin)
         _, x = self.norm.presummed(h) if delta is PRESUMMED else self.norm(h, delta)
         logits = linear(x, self.head_weight())
         if targets is None:

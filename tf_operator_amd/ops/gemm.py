@@ -273,25 +273,29 @@ class first_step:
         return False
 
 
-def _asm_shape_ok(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> bool:
-    """Operands the assembly GEMM takes (csrc/hip/gemm_asm.hip checks the
-    same and refuses anything else): bf16 GPU rows with unit column stride,
-    16-byte aligned rows, M and N multiples of 256 (n_mult), K a multiple of
-    64 and >= 128."""
+def asm_takes(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> bool:
+    """Operands the assembly GEMM takes: the host-side checks of
+    csrc/hip/gemm_asm.hip (``common_ok`` / ``ld_ok`` / ``al16``, which refuse
+    anything else) on x2 [M, K] and w [N, K].  bf16 GPU rows with unit column
+    stride, 16-byte aligned bases, row strides >= K, multiples of 8 and under
+    2^23 elements, M and N multiples of 256 (n_mult), M < 2^28, K a multiple
+    of 64 and >= 128.  The fused epilogues' predicates (ops/llm.py) build on
+    it and add only what their own launcher checks."""
     if not (_MODE == "asm" or _asm_first) or not _lib.has("toa_gemm_asm"):
         return False
     if not (x2.is_cuda and x2.dtype == w.dtype == torch.bfloat16 and x2.dim() == 2 and w.dim() == 2):
         return False
-    if x2.stride(1) != 1 or w.stride(1) != 1 or x2.stride(0) % 8 or w.stride(0) % 8:
-        return False
     M, K = x2.shape
     N = w.shape[0]
-    return (M % 256 == 0 and N % n_mult == 0 and K % 64 == 0 and K >= 128 and w.shape[1] == K
-            and x2.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and _lib.use_hip(x2))
+    for t in (x2, w):
+        if t.stride(1) != 1 or t.stride(0) < K or t.stride(0) % 8 or t.stride(0) >= 1 << 23 or t.data_ptr() % 16:
+            return False
+    return (0 < M < 1 << 28 and M % 256 == 0 and N > 0 and N % n_mult == 0 and K % 64 == 0 and K >= 128
+            and w.shape[1] == K and _lib.use_hip(x2))
 
 
 def linear_fwd(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    if _asm_shape_ok(x2, w):
+    if asm_takes(x2, w):
         M, N = x2.shape[0], w.shape[0]
         y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
         _lib.call("toa_gemm_asm", _lib.ptr(x2), x2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(y), N, M, N,
@@ -307,6 +311,17 @@ def linear_fwd(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     N = w.shape[0]
     y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
     _gemm(1, 0, N, M, K, w, w.stride(0), x2, x2.stride(0), y, N, 0.0)
+    return y
+
+
+def linear_resadd(x2: torch.Tensor, w: torch.Tensor, r2: torch.Tensor) -> torch.Tensor:
+    """y = x2 w^T + r2, the add in the assembly GEMM's epilogue
+    (toa_gemm_asm_resadd: the fp32 sum rounded to bf16 once); r2 [M, N] bf16,
+    contiguous.  For operands ops.llm's ``*_resadd_ok`` predicates passed:
+    anything the launcher refuses raises."""
+    y = torch.empty_like(r2)
+    _lib.call("toa_gemm_asm_resadd", _lib.ptr(x2), x2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(y), y.stride(0),
+              _lib.ptr(r2), x2.shape[0], w.shape[0], x2.shape[1], _lib.stream(x2))
     return y
 
 
@@ -330,7 +345,7 @@ def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def swiglu_gate_up(x2: torch.Tensor, wgu: torch.Tensor):
     """(gu, s) = (x Wgu^T, silu(gate) * up) from ONE assembly GEMM with the
     SwiGLU in its epilogue; None when the kernel cannot take the shapes."""
-    if not (_asm_shape_ok(x2, wgu, n_mult=2) and (wgu.shape[0] // 2) % 128 == 0):
+    if not (asm_takes(x2, wgu, n_mult=2) and (wgu.shape[0] // 2) % 128 == 0):
         return None
     M, F = x2.shape[0], wgu.shape[0] // 2
     gu = torch.empty(M, 2 * F, device=x2.device, dtype=x2.dtype)
@@ -345,7 +360,7 @@ def swiglu_down_dgrad(d2: torch.Tensor, wd: torch.Tensor, gu: torch.Tensor):
     transposed weight copy (ops/wt.py) with the SwiGLU backward in its
     epilogue (ds is never stored); None when the kernel cannot take it."""
     wdt = getattr(wd, "_toa_wt", None)
-    if wdt is None or not (_asm_shape_ok(d2, wdt) and gu.is_contiguous() and gu.shape[1] == 2 * wdt.shape[0]
+    if wdt is None or not (asm_takes(d2, wdt) and gu.is_contiguous() and gu.shape[1] == 2 * wdt.shape[0]
                            and gu.data_ptr() % 16 == 0):
         return None
     M, F = d2.shape[0], wdt.shape[0]

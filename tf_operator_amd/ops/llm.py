@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import gemm
 from .grad import accumulate_mm
+from .linear import linear
 
 
 # ---------------------------------------------------------------------------
@@ -47,6 +48,17 @@ def _rope_ref(x, cos, sin):
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1)
 
 
+def _rope_fwd(qkv, cos, sin, B, S, Hq, Hkv, D, rep):
+    """toa_rope_fwd: rotated, head-major q [B,Hq,S,D] and k / v [B,Hkv*rep,S,D] from qkv."""
+    qkv = qkv.contiguous()
+    q = torch.empty(B, Hq, S, D, device=qkv.device, dtype=qkv.dtype)
+    k = torch.empty(B, Hkv * rep, S, D, device=qkv.device, dtype=qkv.dtype)
+    v = torch.empty_like(k)
+    _lib.call("toa_rope_fwd", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v),
+              B, S, Hq, Hkv, D, rep, _lib.stream(qkv))
+    return q, k, v
+
+
 class _RopeQKV(torch.autograd.Function):
     """qkv [B*S, (Hq+2Hkv)*D] -> q [B,Hq,S,D], k/v [B,Hkv*rep,S,D]."""
 
@@ -55,15 +67,8 @@ class _RopeQKV(torch.autograd.Function):
         ctx.dims = (B, S, Hq, Hkv, D, rep)
         ctx.dtype = qkv.dtype
         ctx.save_for_backward(cos, sin)
-        Hk = Hkv * rep
         if _lib.use_hip(qkv):
-            qkv = qkv.contiguous()
-            q = torch.empty(B, Hq, S, D, device=qkv.device, dtype=qkv.dtype)
-            k = torch.empty(B, Hk, S, D, device=qkv.device, dtype=qkv.dtype)
-            v = torch.empty(B, Hk, S, D, device=qkv.device, dtype=qkv.dtype)
-            _lib.call("toa_rope_fwd", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(q), _lib.ptr(k),
-                      _lib.ptr(v), B, S, Hq, Hkv, D, rep, _lib.stream(qkv))
-            return q, k, v
+            return _rope_fwd(qkv, cos, sin, B, S, Hq, Hkv, D, rep)
         x = qkv.view(B, S, Hq + 2 * Hkv, D).transpose(1, 2)
         q = _rope_ref(x[:, :Hq], cos, sin).to(qkv.dtype)
         k = _rope_ref(x[:, Hq:Hq + Hkv], cos, sin).to(qkv.dtype)
@@ -177,12 +182,8 @@ class _SwiGLUMLP(torch.autograd.Function):
             s = swiglu(gu)
         ctx.save_for_backward(x, wgu, wd, gu, s)
         ctx.has_res = residual is not None
-        if residual is not None:   # + residual in the down projection's epilogue (toa_gemm_asm_resadd)
-            r2 = residual.reshape(s.shape[0], -1)
-            out = torch.empty_like(r2)
-            _lib.call("toa_gemm_asm_resadd", _lib.ptr(s), s.stride(0), _lib.ptr(wd), wd.stride(0), _lib.ptr(out),
-                      out.stride(0), _lib.ptr(r2), s.shape[0], wd.shape[0], s.shape[1], _lib.stream(s))
-            return out.view_as(residual)
+        if residual is not None:   # + residual in the down projection's epilogue
+            return gemm.linear_resadd(s, wd, residual.reshape(s.shape[0], -1)).view_as(residual)
         return gemm.linear_fwd(s, wd).view(*x.shape[:-1], wd.shape[0])
 
     @staticmethod
@@ -208,8 +209,6 @@ def swiglu_mlp(x, wgu, wd, residual=None):
     5, see ops.gemm.resolve_auto), else the two-GEMM + SwiGLU path (``nosk``)."""
     if gemm.mode() == "asm":
         return _SwiGLUMLP.apply(x, wgu, wd, residual)
-    from .linear import linear
-
     out = swiglu_down(linear(x, wgu), wd)
     return out if residual is None else out + residual
 
@@ -221,13 +220,20 @@ def resadd_fused_enabled() -> bool:
     return os.environ.get("TOA_RESADD_FUSED", "1") != "0"
 
 
+def _resadd_ok(a2, w, residual, M) -> bool:
+    """gemm.linear_resadd takes out [M, N] = a w^T + residual: operands the
+    assembly GEMM takes (a2 has a's row layout) and a bf16, contiguous,
+    16-byte aligned residual of the output's size."""
+    return (gemm.mode() == "asm" and gemm.asm_takes(a2, w) and 0 < M < 1 << 28 and M % 256 == 0
+            and residual.dtype == torch.bfloat16 and residual.is_contiguous() and residual.data_ptr() % 16 == 0
+            and residual.numel() == M * w.shape[0] and _lib.has("toa_gemm_asm_resadd") and resadd_fused_enabled())
+
+
 def swiglu_mlp_resadd_ok(x, wd, residual) -> bool:
-    """The residual add fits the fused MLP's down-projection epilogue."""
-    T = x.reshape(-1, x.shape[-1]).shape[0]
-    return (x.is_cuda and residual.dtype == wd.dtype == torch.bfloat16 and gemm.mode() == "asm"
-            and wd.is_contiguous() and residual.is_contiguous() and T % 256 == 0 and wd.shape[0] % 256 == 0
-            and wd.shape[1] % 64 == 0 and residual.numel() == T * wd.shape[0]
-            and _lib.has("toa_gemm_asm_resadd") and resadd_fused_enabled())
+    """The residual add fits the fused MLP's down-projection epilogue.  The
+    projection's input s = swiglu(x Wgu^T) is allocated in the forward,
+    [T, F] contiguous: wd's own rows [N, F] have that layout and stand in."""
+    return x.is_cuda and wd.is_contiguous() and _resadd_ok(wd, wd, residual, x.numel() // x.shape[-1])
 
 
 # ---------------------------------------------------------------------------
@@ -296,18 +302,23 @@ def _attn_hip_ok(q):
             and _lib.has("toa_attn_bwd"))
 
 
+def _attn_fwd(q, k, v, scale, bshd):
+    """toa_attn_fwd: (O, LSE [B, H, S] fp32) of causal attention; O as [B, S, H, D] with bshd."""
+    B, H, S, D = q.shape
+    o = torch.empty(B, S, H, D, device=q.device, dtype=q.dtype) if bshd else torch.empty_like(q)
+    lse = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
+    _lib.call("toa_attn_fwd", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), B, H, k.shape[1], S,
+              D, 1 | (2 if bshd else 0), float(scale), _lib.stream(q))
+    return o, lse
+
+
 class _FlashAttn(torch.autograd.Function):
     """HIP flash attention.  bshd=True returns O as [B, S, H, D] (what the
     output projection reads) and takes dO in that layout: no transpose copies."""
 
     @staticmethod
     def forward(ctx, q, k, v, scale, bshd=False):
-        B, H, S, D = q.shape
-        Hk = k.shape[1]
-        o = torch.empty(B, S, H, D, device=q.device, dtype=q.dtype) if bshd else torch.empty_like(q)
-        lse = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
-        _lib.call("toa_attn_fwd", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), B, H, Hk, S, D,
-                  1 | (2 if bshd else 0), float(scale), _lib.stream(q))
+        o, lse = _attn_fwd(q, k, v, scale, bshd)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
         ctx.bshd = bshd
@@ -344,6 +355,27 @@ def _attn_bwd(q, k, v, o, lse, do, scale, bshd):
 _ROPE_FUSED_BWD = os.environ.get("TOA_ATTN_ROPE_FUSED", "1") != "0"
 
 
+class _DeltaLink:
+    """One attention sub-block forward's hand-off: _AttnOutProj.backward puts
+    the -delta rows its data-gradient GEMM wrote, the attention node's
+    backward takes them (dO is matched on address and size: the reshape
+    between the nodes makes it another tensor object).  Dies with the graph."""
+
+    __slots__ = ("do_ptr", "numel", "ndelta")
+
+    def __init__(self):
+        self.do_ptr = self.numel = self.ndelta = None
+
+    def put(self, do, ndelta):
+        self.do_ptr, self.numel, self.ndelta = do.data_ptr(), do.numel(), ndelta
+
+    def take(self, do):
+        """The rows put for this dO, else None; the link is empty afterwards."""
+        nd = self.ndelta if (self.do_ptr, self.numel) == (do.data_ptr(), do.numel()) else None
+        self.do_ptr = self.numel = self.ndelta = None
+        return nd
+
+
 class _RopeAttn(torch.autograd.Function):
     """RoPE + causal attention as one autograd node (packed K/V, one copy
     per kv head).  Forward: toa_rope_fwd, then the flash-attention forward.
@@ -353,46 +385,34 @@ class _RopeAttn(torch.autograd.Function):
     the attention backward + toa_rope_bwd."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, B, S, Hq, Hkv, D, scale, bshd):
-        qkv = qkv.contiguous()
-        q = torch.empty(B, Hq, S, D, device=qkv.device, dtype=qkv.dtype)
-        k = torch.empty(B, Hkv, S, D, device=qkv.device, dtype=qkv.dtype)
-        v = torch.empty(B, Hkv, S, D, device=qkv.device, dtype=qkv.dtype)
-        _lib.call("toa_rope_fwd", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v),
-                  B, S, Hq, Hkv, D, 1, _lib.stream(qkv))
-        o = torch.empty(B, S, Hq, D, device=q.device, dtype=q.dtype) if bshd else torch.empty_like(q)
-        lse = torch.empty(B, Hq, S, device=q.device, dtype=torch.float32)
-        _lib.call("toa_attn_fwd", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), B, Hq, Hkv, S, D,
-                  1 | (2 if bshd else 0), float(scale), _lib.stream(q))
+    def forward(ctx, qkv, cos, sin, B, S, Hq, Hkv, D, scale, bshd, link):
+        q, k, v = _rope_fwd(qkv, cos, sin, B, S, Hq, Hkv, D, 1)
+        o, lse = _attn_fwd(q, k, v, scale, bshd)
         ctx.save_for_backward(q, k, v, o, lse, cos, sin)
-        ctx.scale, ctx.bshd = scale, bshd
+        ctx.scale, ctx.bshd, ctx.link = scale, bshd, link
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse, cos, sin = ctx.saved_tensors
-        dqkv = _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, ctx.scale, ctx.bshd)
-        return dqkv, None, None, None, None, None, None, None, None, None
+        do = do.contiguous()
+        ndelta = ctx.link.take(do) if ctx.link is not None else None
+        dqkv = _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, ctx.scale, ctx.bshd, ndelta)
+        return dqkv, None, None, None, None, None, None, None, None, None, None
 
 
-# (dO data_ptr, numel, -delta rows) left by the output projection's backward
-# (_AttnOutProj: toa_gemm_asm_delta) for the attention backward that follows
-_PENDING_DELTA = None
-
-
-def _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, scale, bshd):
-    """d(qkv) [B S, (Hq + 2 Hkv) D] of RoPE + causal attention from dO."""
-    global _PENDING_DELTA
+def _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, scale, bshd, ndelta=None):
+    """d(qkv) [B S, (Hq + 2 Hkv) D] of RoPE + causal attention from a
+    contiguous dO; ndelta: the -delta rows [B Hq S] fp32 of this dO where the
+    output projection's data-gradient GEMM wrote them (no delta pass then)."""
     B, Hq, S, D = q.shape
     Hkv = k.shape[1]
-    do = do.contiguous()
-    pend, _PENDING_DELTA = _PENDING_DELTA, None
     dqkv = torch.empty(B * S, (Hq + 2 * Hkv) * D, device=q.device, dtype=q.dtype)
     flags = 1 | (2 if bshd else 0)
     ws = _attn_ws(B, Hq, S, D, q.device)
     if ws is not None and _ROPE_FUSED_BWD and _lib.has("toa_attn_bwd_rope"):
-        if pend is not None and bshd and pend[0] == do.data_ptr() and pend[1] == do.numel():
-            delta = pend[2].view(B, Hq, S)   # the -delta rows from the projection's GEMM: no delta pass
+        if ndelta is not None and bshd:
+            delta = ndelta.view(B, Hq, S)
             flags |= 4
         else:
             delta = torch.empty(B, Hq, S, device=q.device, dtype=torch.float32)
@@ -414,35 +434,29 @@ class _AttnOutProj(torch.autograd.Function):
     """The attention output projection linear(o, wo) whose backward also
     writes the attention backward's -delta rows: its data-gradient GEMM
     (toa_gemm_asm_delta) dots each stored dO row with O per head in its
-    epilogue, so the attention backward (_rope_attn_dqkv) skips its pass over
-    dO and O.  Elsewhere (no W^T copy, other shapes) the plain linear."""
+    epilogue and puts them into the sub-block's link, so the attention
+    backward (_rope_attn_dqkv) skips its pass over dO and O.  Elsewhere (no
+    link, no W^T copy, other shapes) the plain linear."""
 
     @staticmethod
-    def forward(ctx, o2, wo, B, S, H, residual=None):
+    def forward(ctx, o2, wo, B, S, H, residual, link):
         ctx.save_for_backward(o2, wo)
         ctx.dims = (B, S, H)
-        ctx.has_res = residual is not None
+        ctx.has_res, ctx.link = residual is not None, link
         if residual is None:
             return gemm.linear_fwd(o2, wo)
-        # the residual add in the GEMM's epilogue (toa_gemm_asm_resadd): out = o2 wo^T + residual
-        r2 = residual.reshape(o2.shape[0], -1)
-        out = torch.empty_like(r2)
-        _lib.call("toa_gemm_asm_resadd", _lib.ptr(o2), o2.stride(0), _lib.ptr(wo), wo.stride(0), _lib.ptr(out),
-                  out.stride(0), _lib.ptr(r2), o2.shape[0], wo.shape[0], o2.shape[1], _lib.stream(o2))
-        return out.view_as(residual)
+        # the residual add in the GEMM's epilogue: out = o2 wo^T + residual
+        return gemm.linear_resadd(o2, wo, residual.reshape(o2.shape[0], -1)).view_as(residual)
 
     @staticmethod
     def backward(ctx, dy):
-        global _PENDING_DELTA
-        from .grad import accumulate_mm
-
         o2, wo = ctx.saved_tensors
         B, S, H = ctx.dims
         dy2 = dy.reshape(-1, dy.shape[-1])
         dx = None
         wt = getattr(wo, "_toa_wt", None)
-        if (ctx.needs_input_grad[0] and wt is not None and dy2.stride(-1) == 1 and wt.stride(-1) == 1
-                and o2.is_contiguous() and os.environ.get("TOA_ATTN_DELTA_FUSED", "1") != "0"
+        if (ctx.needs_input_grad[0] and ctx.link is not None and wt is not None and dy2.stride(-1) == 1
+                and wt.stride(-1) == 1 and o2.is_contiguous() and attn_delta_fused_enabled()
                 and _lib.has("toa_gemm_asm_delta") and gemm.mode() == "asm"):
             T, N = o2.shape
             dx = torch.empty_like(o2)
@@ -451,7 +465,7 @@ class _AttnOutProj(torch.autograd.Function):
                                _lib.ptr(dx), dx.stride(0), _lib.ptr(o2), _lib.ptr(nd), T, N, dy2.shape[1], S, H,
                                _lib.stream(dy2))
             if rc == 0:
-                _PENDING_DELTA = (dx.data_ptr(), dx.numel(), nd)
+                ctx.link.put(dx, nd)
             elif rc == 1:   # hipErrorInvalidValue: a shape it does not take
                 dx = None
             else:
@@ -459,36 +473,31 @@ class _AttnOutProj(torch.autograd.Function):
         if dx is None and ctx.needs_input_grad[0]:
             dx = gemm.linear_dgrad(dy2, wo)
         dw = accumulate_mm(wo, dy2.t(), o2)
-        return dx, dw, None, None, None, (dy if ctx.has_res else None)
+        return dx, dw, None, None, None, (dy if ctx.has_res else None), None
 
 
-def attn_out_proj(o2, wo, B, S, H, residual=None):
-    """linear(o2, wo) (+ residual, added in the GEMM's epilogue) for the
-    attention output o2 [B S, H 128]; its backward hands the attention
-    backward its delta rows."""
-    return _AttnOutProj.apply(o2, wo, B, S, H, residual)
+def attn_delta_fused_enabled() -> bool:
+    """The attention backward's delta rows from the output projection's data
+    gradient (TOA_ATTN_DELTA_FUSED=0: the attention's own delta pass)."""
+    return os.environ.get("TOA_ATTN_DELTA_FUSED", "1") != "0"
+
+
+def attn_out_proj(o2, wo, B, S, H, residual=None, link=None):
+    """linear(o2, wo) (+ residual, added in the GEMM's epilogue where
+    attn_out_proj_resadd_ok) for the attention output o2 [B S, H 128]; with
+    the _DeltaLink its attention node got, its backward hands that node's
+    backward the delta rows."""
+    return _AttnOutProj.apply(o2, wo, B, S, H, residual, link)
 
 
 def attn_out_proj_resadd_ok(o2, wo, residual) -> bool:
     """The residual add fits the output projection's epilogue (TOA_RESADD_FUSED)."""
-    return (o2.is_cuda and o2.dtype == wo.dtype == residual.dtype == torch.bfloat16 and gemm.mode() == "asm"
-            and o2.is_contiguous() and wo.is_contiguous() and residual.is_contiguous()
-            and o2.shape[0] % 256 == 0 and wo.shape[0] % 256 == 0 and o2.shape[1] % 64 == 0
-            and residual.numel() == o2.shape[0] * wo.shape[0] and _lib.has("toa_gemm_asm_resadd")
-            and resadd_fused_enabled())
+    return _resadd_ok(o2, wo, residual, o2.shape[0])
 
 
-_COSSIN: dict = {}   # (cos ptr, sin ptr, S) -> cos | sin [2][S][64] fp32 (toa_gemm_asm_rope's table)
-
-
-def _cossin(cos, sin):
-    key = (cos.data_ptr(), sin.data_ptr(), cos.shape[0])
-    t = _COSSIN.get(key)
-    if t is None:
-        if len(_COSSIN) > 16:
-            _COSSIN.clear()
-        t = _COSSIN[key] = torch.stack([cos.float(), sin.float()]).contiguous()
-    return t
+def rope_cossin(cos, sin):
+    """cos | sin [2][S][64] fp32, the table toa_gemm_asm_rope reads."""
+    return torch.stack([cos.float(), sin.float()])
 
 
 class _QKVRopeAttn(torch.autograd.Function):
@@ -500,59 +509,61 @@ class _QKVRopeAttn(torch.autograd.Function):
     gradients (ops/linear.py)."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, cos, sin, B, S, Hq, Hkv, D, scale, bshd):
+    def forward(ctx, x, wqkv, cos, sin, cossin, B, S, Hq, Hkv, D, scale, bshd, link):
         x2 = x.reshape(-1, x.shape[-1])
         T, K = x2.shape
         out = torch.empty(T * (Hq + 2 * Hkv) * D, device=x.device, dtype=x.dtype)
-        cs = _cossin(cos, sin)
         _lib.call("toa_gemm_asm_rope", _lib.ptr(x2), x2.stride(0), _lib.ptr(wqkv), wqkv.stride(0), _lib.ptr(out),
-                  _lib.ptr(cs), T, K, S, Hq, Hkv, _lib.stream(x2))
+                  _lib.ptr(cossin), T, K, S, Hq, Hkv, _lib.stream(x2))
         nq, nk = B * Hq * S * D, B * Hkv * S * D
         q = out[:nq].view(B, Hq, S, D)
         k = out[nq:nq + nk].view(B, Hkv, S, D)
         v = out[nq + nk:].view(B, Hkv, S, D)
-        o = torch.empty(B, S, Hq, D, device=x.device, dtype=x.dtype) if bshd else torch.empty_like(q)
-        lse = torch.empty(B, Hq, S, device=x.device, dtype=torch.float32)
-        _lib.call("toa_attn_fwd", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), B, Hq, Hkv, S, D,
-                  1 | (2 if bshd else 0), float(scale), _lib.stream(q))
+        o, lse = _attn_fwd(q, k, v, scale, bshd)
         ctx.save_for_backward(x, wqkv, q, k, v, o, lse, cos, sin)
-        ctx.scale, ctx.bshd = scale, bshd
+        ctx.scale, ctx.bshd, ctx.link = scale, bshd, link
         return o
 
     @staticmethod
     def backward(ctx, do):
-        from .grad import accumulate_mm
-
         x, wqkv, q, k, v, o, lse, cos, sin = ctx.saved_tensors
-        dqkv = _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, ctx.scale, ctx.bshd)
+        do = do.contiguous()
+        ndelta = ctx.link.take(do) if ctx.link is not None else None
+        dqkv = _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, ctx.scale, ctx.bshd, ndelta)
         x2 = x.reshape(-1, x.shape[-1])
         dx = gemm.linear_dgrad(dqkv, wqkv).view_as(x) if ctx.needs_input_grad[0] else None
         dw = accumulate_mm(wqkv, dqkv.t(), x2)
-        return dx, dw, None, None, None, None, None, None, None, None, None
+        return (dx, dw) + (None,) * 11
 
 
 def qkv_rope_attention_ok(x, wqkv, S, Hq, Hkv, D) -> bool:
-    """The fused projection + RoPE path applies: the assembly GEMM policy,
-    bf16, head dim 128, S and the projection width multiples of 256."""
-    return (x.is_cuda and x.dtype == wqkv.dtype == torch.bfloat16 and D == 128 and S % 256 == 0
-            and ((Hq + 2 * Hkv) * D) % 256 == 0 and Hq % Hkv == 0 and gemm.mode() == "asm"
-            and os.environ.get("TOA_QKV_ROPE", "1") != "0" and _lib.has("toa_gemm_asm_rope")
-            and x.reshape(-1, x.shape[-1]).stride(-1) == 1 and wqkv.stride(-1) == 1
-            and (x.reshape(-1, x.shape[-1]).shape[0]) % S == 0 and x.shape[-1] % 64 == 0)
+    """The fused projection + RoPE path applies: the assembly policy,
+    operands the assembly GEMM takes (N = (Hq + 2 Hkv) 128 a multiple of 256
+    among them) and what toa_gemm_asm_rope checks on top -- head dim 128, S a
+    multiple of 256 dividing M, its head-count and 32-bit offset limits."""
+    x2 = x.reshape(-1, x.shape[-1])
+    M, N = x2.shape[0], wqkv.shape[0]
+    return (gemm.mode() == "asm" and gemm.asm_takes(x2, wqkv) and D == 128 and N == (Hq + 2 * Hkv) * D
+            and S > 0 and S % 256 == 0 and M % S == 0 and 0 < Hkv <= Hq <= 4096 and Hq % Hkv == 0
+            and M * N * 2 < 2 ** 32 and S * 512 + 128 * 256 < 2 ** 32
+            and os.environ.get("TOA_QKV_ROPE", "1") != "0" and _lib.has("toa_gemm_asm_rope"))
 
 
-def qkv_rope_attention(x, wqkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd"):
-    """linear(x, wqkv) -> rope_attention, fused where qkv_rope_attention_ok."""
+def qkv_rope_attention(x, wqkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd", cossin=None, link=None):
+    """linear(x, wqkv) -> rope_attention, fused where qkv_rope_attention_ok.
+    cossin: rope_cossin(cos, sin), built for this call when not passed (a
+    model keeps its own, models/llama.py); link: see attn_out_proj."""
     scale = 1.0 / math.sqrt(D) if scale is None else scale
-    return _QKVRopeAttn.apply(x, wqkv, cos, sin, B, S, Hq, Hkv, D, scale, out_layout == "bshd")
+    cossin = rope_cossin(cos, sin) if cossin is None else cossin
+    return _QKVRopeAttn.apply(x, wqkv, cos, sin, cossin, B, S, Hq, Hkv, D, scale, out_layout == "bshd", link)
 
 
-def rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd"):
+def rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd", link=None):
     """RoPE (Llama rotate-half, cos / sin [S, D/2]) on the fused QKV
     projection [B*S, (Hq + 2 Hkv) D], then causal attention with packed GQA:
     O as [B, S, Hq, D] (out_layout="bshd") or [B, Hq, S, D].  On the GPU one
-    autograd node (_RopeAttn) whose backward writes d(qkv) directly; on the
-    CPU rope_qkv + causal_attention."""
+    autograd node (_RopeAttn) whose backward writes d(qkv) directly (link: see
+    attn_out_proj); on the CPU rope_qkv + causal_attention."""
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     if qkv.is_cuda:
         if not (qkv.dtype == torch.bfloat16 and D in ATTN_HEAD_DIMS and _lib.has("toa_attn_fwd")
@@ -561,9 +572,30 @@ def rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd
                                f"(got {qkv.dtype}, head_dim {D}; library: {_lib.load_error() or 'ok'})")
         if Hq % Hkv:
             raise ValueError(f"query heads {Hq} not a multiple of kv heads {Hkv}")
-        return _RopeAttn.apply(qkv, cos, sin, B, S, Hq, Hkv, D, scale, out_layout == "bshd")
+        return _RopeAttn.apply(qkv, cos, sin, B, S, Hq, Hkv, D, scale, out_layout == "bshd", link)
     q, k, v = rope_qkv(qkv, cos, sin, B, S, Hq, Hkv, D, 1)
     return causal_attention(q, k, v, scale, out_layout)
+
+
+def attention_block(x, wqkv, wo, cos, sin, B, S, Hq, Hkv, D, residual=None, kv_layout="auto", cossin=None):
+    """QKV projection, RoPE, causal attention and output projection on the
+    normalised x [B S, hidden].  Returns (out, summed): summed where the
+    projection's epilogue added the residual (else the caller's norm adds it).
+    Packed K/V: one node for projection + RoPE + attention where
+    qkv_rope_attention_ok, else linear + rope_attention, sharing a _DeltaLink
+    with the output projection on the GPU; "expand": K/V per query head."""
+    packed = kv_layout in ("packed", "auto")
+    link = _DeltaLink() if packed and x.is_cuda else None
+    if packed and qkv_rope_attention_ok(x, wqkv, S, Hq, Hkv, D):
+        o = qkv_rope_attention(x, wqkv, cos, sin, B, S, Hq, Hkv, D, cossin=cossin, link=link)
+    elif packed:
+        o = rope_attention(linear(x, wqkv), cos, sin, B, S, Hq, Hkv, D, link=link)
+    else:
+        q, k, v = rope_qkv(linear(x, wqkv), cos, sin, B, S, Hq, Hkv, D)
+        o = causal_attention(q, k, v, out_layout="bshd")
+    o = o.reshape(B * S, Hq * D)   # [B, S, H, D] from every path: no transpose copy on the GPU
+    summed = residual is not None and link is not None and attn_out_proj_resadd_ok(o, wo, residual)
+    return attn_out_proj(o, wo, B, S, Hq, residual if summed else None, link), summed
 
 
 def _attention_reference(q, k, v, scale):

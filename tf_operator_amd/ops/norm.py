@@ -53,8 +53,8 @@ class _NormFn(torch.autograd.Function):
         rows = x2.shape[0]
         if not x2.is_contiguous():
             x2 = x2.contiguous()
-        # residual == "presummed": x already holds the residual sum (the output
-        # projection's GEMM added it, ops/llm._AttnOutProj): no add, h is x
+        # residual == "presummed": x already holds the residual sum (a projection's
+        # GEMM added it in its epilogue, ops/gemm.linear_resadd): no add, h is x
         presum = isinstance(residual, str)
         r2 = residual.reshape(-1, cols).contiguous() if residual is not None and not presum else None
         if _lib.use_hip(x2):

@@ -10,7 +10,12 @@ lands in LDS, every fragment a lane reads, every output element) -- not the
 timing of waits, which the schedule's vmcnt / barrier placement is reasoned
 about in the generator's docstring.  Any buffer access outside its
 resource's num_records raises, so a bounds bug fails the CPU test instead of
-being silently zero-filled on the GPU.
+being silently zero-filled on the GPU.  ``Emu(..., hw_bounds=True)`` opts
+into the hardware's range check instead (the token-tail kernels rely on it):
+per lane, a load past num_records reads 0 (an LDS-DMA lane writes 0 into
+LDS) and a store past it is dropped, both counted (``oob_loads`` /
+``oob_stores``, in lanes); the in-range lanes must still fall inside a
+``Memory`` buffer.
 
 Used by tests/test_asm_gemm.py; no GPU, no assembler needed.
 """
@@ -100,9 +105,11 @@ class Emu:
     output wrong, as it would be on the hardware.  With strict_vm False every
     load lands at issue (the round-5 model)."""
 
-    def __init__(self, asm_text: str, kernel: str, strict_vm: bool = True):
+    def __init__(self, asm_text: str, kernel: str, strict_vm: bool = True, hw_bounds: bool = False):
         self.prog, self.labels = self._parse(asm_text, kernel)
         self.strict_vm = strict_vm
+        self.hw_bounds = hw_bounds
+        self.oob_loads = self.oob_stores = 0
 
     def _vm_issue(self, w, effect):
         """Queue a VMEM op's effect (None for a store: its memory write is
@@ -654,21 +661,35 @@ class Emu:
             if md.startswith("offset:"):
                 ioff = int(md.split(":")[1])
         off = voff + soff + ioff
-        if int(off.max()) + nbytes > nrec:
+        self._ok = off + nbytes <= nrec          # per lane, for the _gread / _gwrite that follows
+        if not self._ok.all() and not self.hw_bounds:
             raise IndexError(f"buffer access past num_records ({int(off.max())} + {nbytes} > {nrec})")
         return base + off
 
     def _gread(self, addr, nbytes):
-        base, buf = self.mem.locate(addr, nbytes)
-        rel = (addr - base).astype(np.int64)
-        return np.stack([buf[rel + i] for i in range(nbytes)], axis=1)  # [64, nbytes]
+        """[64, nbytes] of the access _buffer_addr just resolved; with
+        hw_bounds its out-of-range lanes read 0."""
+        ok = self._ok
+        out = np.zeros((64, nbytes), np.uint8)
+        self.oob_loads += int((~ok).sum())
+        if ok.any():
+            base, buf = self.mem.locate(addr[ok], nbytes)
+            rel = (addr[ok] - base).astype(np.int64)
+            out[ok] = np.stack([buf[rel + i] for i in range(nbytes)], axis=1)
+        return out
 
     def _gwrite(self, addr, data):
+        """with hw_bounds the out-of-range lanes of the access _buffer_addr
+        just resolved store nothing."""
+        ok = self._ok
         nbytes = data.shape[1]
-        base, buf = self.mem.locate(addr, nbytes)
-        rel = (addr - base).astype(np.int64)
+        self.oob_stores += int((~ok).sum())
+        if not ok.any():
+            return
+        base, buf = self.mem.locate(addr[ok], nbytes)
+        rel = (addr[ok] - base).astype(np.int64)
         for i in range(nbytes):
-            buf[rel + i] = data[:, i]
+            buf[rel + i] = data[ok, i]
 
     def op_buffer_load_dwordx4(self, w, a, mods):
         if "lds" not in mods:

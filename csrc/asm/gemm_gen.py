@@ -86,8 +86,12 @@ KARG = {
     "X": 0, "W": 8, "C": 16, "S": 24,
     "ldx": 32, "ldw": 36, "ldc": 40, "lds": 44,
     "ktiles": 48, "tiles_m": 52, "tiles_n": 56, "xq": 60, "xr": 64,
-    "per_group": 68, "fw": 72, "fc": 76, "map": 80, "grid": 84, "phase": 88,
+    "per_group": 68, "fw": 72, "fc": 76, "map": 80, "grid": 84, "phase": 88, "m": 92,
 }
+# `m`: the rows of X / C (0 = tiles_m whole tiles).  tiles_m = ceil(m / 256);
+# the last tile row's X / C / S resources end at row m, so the hardware's
+# range check zero-fills the loads and drops the stores of the rows past it
+# (the delta kernel's bytes 88..95 are a pointer: whole tiles only).
 MAP_WALK_COLS = 16
 MAP_DEFAULT = 2          # groups of 4 row tiles walk the column tiles
 
@@ -99,7 +103,7 @@ S_ARGS = 4          # s[4:23]: the 80 B of kernarg
 S_X, S_W, S_C, S_S = 4, 6, 8, 10
 S_LDX, S_LDW, S_LDC, S_LDS = 12, 13, 14, 15
 S_KT, S_TM_N, S_TN_N, S_XQ = 16, 17, 18, 19
-S_XR, S_PG, S_FW, S_FC = 20, 21, 22, 23
+S_XR, S_M, S_FW, S_FC = 20, 21, 22, 23   # S_M: rows of X / C (kernarg `m`; the per_group word is not used)
 S_TILE, S_TM, S_TN = 24, 25, 26
 S_T0, S_T1, S_T2, S_T3 = 27, 28, 29, 30
 S_PHASE = 31        # kernarg `phase` word (start offsets of the first wave, phase_delay)
@@ -226,6 +230,8 @@ def prologue_args(a: Asm, epi: str = "plain"):
     a(f"s_load_dwordx4 {sr(S_ARGS + 16, 4)}, s[0:1], 0x40")
     a(f"s_load_dwordx2 {sr(S_MAP, 2)}, s[0:1], 0x50")
     a(f"s_load_dword {sr(S_PHASE)}, s[0:1], {KARG['phase']:#x}")
+    if epi != "delta":
+        a(f"s_load_dword {sr(S_E0)}, s[0:1], {KARG['m']:#x}")
     a("s_mov_b32 m0, 0")
     a(f"v_mov_b32 {vr(V_TID)}, v0")
     a("s_waitcnt lgkmcnt(0)")
@@ -242,6 +248,15 @@ def prologue_args(a: Asm, epi: str = "plain"):
     a(f"s_add_u32 {sr(S_T1)}, {sr(S_T1)}, {sr(S_XR)}")
     a(f"s_cmp_lg_u32 {sr(S_T1)}, {sr(S_T0)}")
     a(f"s_cbranch_scc1 {a.abort}")
+    # rows: m = 0 means whole tiles; else (tiles_m - 1) 256 < m <= tiles_m 256
+    a(f"s_lshl_b32 {sr(S_M)}, {sr(S_TM_N)}, 8")
+    if epi != "delta":
+        a(f"s_cmp_eq_u32 {sr(S_E0)}, 0")
+        a(f"s_cselect_b32 {sr(S_E0)}, {sr(S_M)}, {sr(S_E0)}")
+        a(f"s_sub_u32 {sr(S_T1)}, {sr(S_M)}, {sr(S_E0)}")
+        a(f"s_cmp_ge_u32 {sr(S_T1)}, 256")      # (m > tiles_m 256 wraps to a huge value)
+        a(f"s_cbranch_scc1 {a.abort}")
+        a(f"s_mov_b32 {sr(S_M)}, {sr(S_E0)}")
     # tile order: log2 group <= 6, nothing above the walk bit
     a(f"s_and_b32 {sr(S_LG)}, {sr(S_MAP)}, 15")
     a(f"s_cmp_gt_u32 {sr(S_LG)}, 6")
@@ -316,8 +331,8 @@ def tile_setup(a: Asm, epi: str, bid: str = "s2"):
     a(f"s_cmp_eq_u32 {sr(S_WALK)}, 0")
     a(f"s_cselect_b32 {sr(S_E0)}, {sr(S_TM_N)}, {sr(S_TN_N)}")
     a(f"s_cselect_b32 {sr(S_E1)}, {sr(S_TN_N)}, {sr(S_TM_N)}")
-    a(f"s_lshl_b32 {sr(S_PG)}, {sr(S_E1)}, {sr(S_LG)}")   # tiles per group (the kernarg's is not used)
-    udiv(a, S_Q, S_R, S_TILE, S_PG)                     # group, within
+    a(f"s_lshl_b32 {sr(S_T3)}, {sr(S_E1)}, {sr(S_LG)}")   # tiles per group
+    udiv(a, S_Q, S_R, S_TILE, S_T3)                     # group, within
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_Q)}, {sr(S_LG)}")  # first tile of the group
     a(f"s_sub_u32 {sr(S_T1)}, {sr(S_E0)}, {sr(S_T0)}")
     a(f"s_lshl_b32 {sr(S_T2)}, 1, {sr(S_LG)}")
@@ -330,10 +345,10 @@ def tile_setup(a: Asm, epi: str, bid: str = "s2"):
     a(f"s_cselect_b32 {sr(S_TN)}, {sr(S_Q)}, {sr(S_T0)}")
 
     # --- buffer resources at the tile's first row / column
-    # X: rows tm*256 .. +255, every k
+    # X: rows tm*256 .. +255 (the last tile row: up to row m), every k
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TM)}, 8")
     mul64(a, S_T2, S_T3, S_T0, S_LDX)
-    a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDX)}, 8")       # 256 rows
+    tile_rows_bytes(a, S_T1, S_LDX)
     srd(a, SRD_X, S_X, S_T2, S_T3, S_T1)
     # W: rows tn*256 (tn*128 for the gate|up projection)
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, {7 if epi == 'swiglu_fwd' else 8}")
@@ -343,6 +358,16 @@ def tile_setup(a: Asm, epi: str, bid: str = "s2"):
         a(f"s_lshr_b32 {sr(S_T1)}, {sr(S_T1)}, 1")    # 128 rows of each half
         a(f"s_add_u32 {sr(S_T1)}, {sr(S_T1)}, {sr(S_FW)}")  # + the up half's offset
     srd(a, SRD_W, S_W, S_T2, S_T3, S_T1)
+
+
+def tile_rows_bytes(a: Asm, dst: int, ld: int):
+    """s[dst] = min(256, m - 256 tm) * s[ld]: num_records of a window over the
+    tile row's live rows.  Row strides are multiples of 16 B, so no 16-B
+    access straddles the bound."""
+    a(f"s_lshl_b32 {sr(dst)}, {sr(S_TM)}, 8")
+    a(f"s_sub_u32 {sr(dst)}, {sr(S_M)}, {sr(dst)}")
+    a(f"s_min_u32 {sr(dst)}, {sr(dst)}, 256")
+    a(f"s_mul_i32 {sr(dst)}, {sr(dst)}, {sr(ld)}")
 
 
 def tile_c(a: Asm, epi: str):
@@ -356,7 +381,7 @@ def tile_c(a: Asm, epi: str):
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, {8 if epi == 'swiglu_fwd' else 9}")  # column bytes
     a(f"s_add_u32 {sr(S_T2)}, {sr(S_T2)}, {sr(S_T0)}")
     a(f"s_addc_u32 {sr(S_T3)}, {sr(S_T3)}, 0")
-    a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDC)}, 8")
+    tile_rows_bytes(a, S_T1, S_LDC)
     srd(a, SRD_C, S_C, S_T2, S_T3, S_T1)
     if epi in ("delta", "resadd"):   # O / the residual: the same tile of a tensor laid out like C
         a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TM)}, 8")
@@ -364,7 +389,7 @@ def tile_c(a: Asm, epi: str):
         a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, 9")
         a(f"s_add_u32 {sr(S_T2)}, {sr(S_T2)}, {sr(S_T0)}")
         a(f"s_addc_u32 {sr(S_T3)}, {sr(S_T3)}, 0")
-        a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDC)}, 8")
+        tile_rows_bytes(a, S_T1, S_LDC)
         srd(a, SRD_S, S_S, S_T2, S_T3, S_T1)
     if epi in ("swiglu_fwd", "swiglu_bwd"):
         a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TM)}, 8")
@@ -372,7 +397,7 @@ def tile_c(a: Asm, epi: str):
         a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, {8 if epi == 'swiglu_fwd' else 9}")
         a(f"s_add_u32 {sr(S_T2)}, {sr(S_T2)}, {sr(S_T0)}")
         a(f"s_addc_u32 {sr(S_T3)}, {sr(S_T3)}, 0")
-        a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDS)}, 8")
+        tile_rows_bytes(a, S_T1, S_LDS)
         srd(a, SRD_S, S_S, S_T2, S_T3, S_T1)
 
 

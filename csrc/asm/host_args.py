@@ -14,10 +14,13 @@ def grid_params(tiles_m: int, tiles_n: int):
 
 
 def pack(X, W, C, S, ldx_b, ldw_b, ldc_b, lds_b, K, tiles_m, tiles_n, fw_b=0, fc_b=0, grid=None,
-         tile_map=MAP_DEFAULT, phase=0) -> bytes:
+         tile_map=MAP_DEFAULT, phase=0, M=None) -> bytes:
     """grid: a persistent kernel's workgroup count; tile_map: the tile order
     (gemm_gen.KARG "map": log2 group | 16 for column groups); phase: the
-    first wave's start offsets (gemm_gen.phase_delay)."""
+    first wave's start offsets (gemm_gen.phase_delay); M: the rows of X / C
+    when the last tile row is partial (tiles_m = ceil(M / 256); None = whole
+    tiles, the word stays 0)."""
+    assert M is None or 256 * (tiles_m - 1) < M <= 256 * tiles_m
     nwg, xq, xr, pg = grid_params(tiles_m, tiles_n)
     buf = bytearray(KARG_BYTES)
     struct.pack_into("<QQQQ", buf, KARG["X"], X, W, C, S)
@@ -25,7 +28,7 @@ def pack(X, W, C, S, ldx_b, ldw_b, ldc_b, lds_b, K, tiles_m, tiles_n, fw_b=0, fc
     struct.pack_into("<IIIIII", buf, KARG["ktiles"], K // 64, tiles_m, tiles_n, xq, xr, pg)
     struct.pack_into("<II", buf, KARG["fw"], fw_b, fc_b)
     struct.pack_into("<II", buf, KARG["map"], tile_map, grid or 0)
-    struct.pack_into("<I", buf, KARG["phase"], phase)
+    struct.pack_into("<II", buf, KARG["phase"], phase, M or 0)
     return bytes(buf)
 
 
@@ -51,28 +54,38 @@ def tile_order(tiles_m: int, tiles_n: int, tile_map: int = MAP_DEFAULT) -> list[
 
 def wgrad_plan(M: int, N: int, K: int) -> tuple[int, int]:
     """(full, split) of csrc/hip/wgrad.hip's wg_plan: whole-K tiles for
-    whole waves of 256 CUs, the tail cut into 2..4 K-pieces that fill it."""
+    whole waves of 256 CUs, the tail cut into 2..4 K-pieces that fill it.
+    A K that is no multiple of 64 (the assembly kernel only:
+    csrc/hip/gemm_asm.hip wgrad_asm_plan) takes the largest such split that
+    divides its ceil(K / 64) k-tiles: pieces are cut at multiples of 64 rows."""
     tiles = (M // 256) * (N // 256)
     rem = tiles % 256
     if rem == 0:
         return tiles, 1
     best = 1
     for s in range(2, 5):
-        if rem * s <= 256 and K % (128 * s) == 0 and K // s >= 512:
+        fits = K % (128 * s) == 0 if K % 64 == 0 else -(-K // 64) % s == 0
+        if rem * s <= 256 and fits and K // s >= 512:
             best = s
     return (tiles, 1) if best == 1 else (tiles - rem, best)
 
 
-def pack_nt(A, B, C, WS, lda_b, ldb_b, ldc_b, beta, K, tiles_m, tiles_n, full, split, tile_map=3, sq=0) -> bytes:
+def pack_nt(A, B, C, WS, lda_b, ldb_b, ldc_b, beta, K, tiles_m, tiles_n, full, split, tile_map=3, sq=0,
+            T=None) -> bytes:
     """The weight-gradient kernel's block (csrc/asm/wgrad_gen.py KARG): the
     same bytes, with beta / full / rem / split in the forward kernels'
     lds / xq / xr / per_group slots and the tile order in the map slot
-    (wgrad_gen.MAP_DEFAULT = 3: groups of 8 row tiles walk the columns)."""
+    (wgrad_gen.MAP_DEFAULT = 3: groups of 8 row tiles walk the columns).
+    T: the reduction length in rows when it is no multiple of 64 (it replaces
+    K: ceil(T / 64) k-tiles and T in wgrad_gen.KARG "t"; None = K rows, the
+    word stays 0)."""
     rem = tiles_m * tiles_n - full
+    ktiles = K // 64 if T is None else -(-T // 64)
     buf = bytearray(KARG_BYTES)
     struct.pack_into("<QQQQ", buf, 0, A, B, C, WS)
     struct.pack_into("<IIII", buf, 32, lda_b, ldb_b, ldc_b, beta)
-    struct.pack_into("<IIIIII", buf, 48, K // 64, tiles_m, tiles_n, full, rem, split)
+    struct.pack_into("<IIIIII", buf, 48, ktiles, tiles_m, tiles_n, full, rem, split)
+    struct.pack_into("<I", buf, 72, T or 0)
     struct.pack_into("<I", buf, KARG["map"], tile_map)
     struct.pack_into("<Q", buf, 88, sq)     # wgrad_gen.KARG "sq": the sum-of-squares partials (0 = off)
     return bytes(buf)

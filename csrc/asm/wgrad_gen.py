@@ -38,7 +38,23 @@ ahead, pieces spread over the iteration); what differs is the LDS image:
 
 Kernarg (80 B, the forward kernels' block; csrc/hip/gemm_asm.hip
 toa_wgrad_asm): A, B, C, WS pointers, lda/ldb/ldc bytes, beta, K tiles of
-the whole T, tiles_m, tiles_n, full, rem, split.
+the whole T, tiles_m, tiles_n, full, rem, split, and T itself in rows at
+byte 72 (0 = 64 * K tiles).
+
+  T tail      K tiles = ceil(T / 64).  The last, partial tile gets its own
+              window: the workgroup that carries it (a whole-K tile, or the
+              last k-piece) stages it FIRST, in the prologue, through
+              resources of (T mod 64) rows, then switches to the usual 64-row
+              window at its first row and runs its other tiles in order -- the
+              main loop is instruction for instruction the one without tails
+              (the order of the sum differs, for tail shapes only).  The rows
+              of that tile past T are out of range: their LDS-DMA lanes write
+              0 into LDS (measured on MI355X, docs/kernels.md), so they add
+              exactly 0 to every accumulator whatever lies behind the operands
+              in memory.  k-pieces stay cut at multiples of 64 rows (the host
+              plan's split divides the K tiles).  No tile t + 2 >= K tiles of
+              the piece is ever prefetched (the last two iterations issue no
+              DMA), and the windows never shrink or wrap.
 
 Reference anchor: SURVEY.md K1/K2 (the training step's GEMMs); the
 reference itself has no kernels.
@@ -69,13 +85,14 @@ def pos(r: int, c: int) -> int:
 
 # kernarg block (byte offsets)
 KARG = {"A": 0, "B": 8, "C": 16, "WS": 24, "lda": 32, "ldb": 36, "ldc": 40, "beta": 44, "ktiles": 48,
-        "tiles_m": 52, "tiles_n": 56, "full": 60, "rem": 64, "split": 68, "map": 80, "sq": 88}
+        "tiles_m": 52, "tiles_n": 56, "full": 60, "rem": 64, "split": 68, "t": 72, "map": 80, "sq": 88}
 MAP_DEFAULT = 3     # groups of 8 row tiles (dW rows) walk the column tiles: the round-4/5 order
 
 # SGPRs
 S_A, S_B, S_C, S_WS = 4, 6, 8, 10
 S_LDA, S_LDB, S_LDC, S_BETA = 12, 13, 14, 15
 S_KT, S_TM_N, S_TN_N, S_FULL, S_REM, S_SPLIT = 16, 17, 18, 19, 20, 21
+S_TROWS = 22        # kernarg "t": the reduction length in rows
 S_TILE, S_TM, S_TN = 24, 25, 26
 S_T0, S_T1, S_T2, S_T3 = 27, 28, 29, 30
 SRD_A, SRD_B, SRD_C, SRD_WS = 32, 36, 40, 44
@@ -89,7 +106,10 @@ S_S, S_J, S_PIECE = 71, 72, 73   # k-piece index, tail tile index, 1 for a k-pie
 S_ADVA, S_ADVB, S_KTP = 74, 75, 76   # 64 lda, 64 ldb, k-tiles of this workgroup
 S_MAPW, S_LG, S_WALK = 77, 78, 79    # kernarg tile order (gemm_gen.KARG "map"): word, log2 group, walk flag
 SRD_SQ = 80         # s80..s83: the sum-of-squares partials (kernarg "sq" in s[80:81]; 0 = off)
-N_SGPR = 84
+S_ROW0, S_ROW1, S_ROWS0 = 84, 85, 86   # first rows of the workgroup's tiles 0 and 1, live rows of tile 0
+S_A1, S_B1 = 88, 90                    # s[88:89], s[90:91]: the operands' tile-1 window bases
+S_NRA, S_NRB = 92, 93                  # num_records of a 64-row window
+N_SGPR = 96
 
 # VGPRs
 V_DA, V_RALO, V_RAHI = 1, 2, 3
@@ -126,6 +146,13 @@ def prologue(a: Asm):
     a(f"s_mul_i32 {sr(S_T1)}, {sr(S_TM_N)}, {sr(S_TN_N)}")
     a(f"s_add_u32 {sr(S_T2)}, {sr(S_FULL)}, {sr(S_REM)}")
     a(f"s_cmp_lg_u32 {sr(S_T1)}, {sr(S_T2)}")
+    a(f"s_cbranch_scc1 {a.abort}")
+    # t = 0 means 64 ktiles; else 64 (ktiles - 1) < t <= 64 ktiles
+    a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_KT)}, 6")
+    a(f"s_cmp_eq_u32 {sr(S_TROWS)}, 0")
+    a(f"s_cselect_b32 {sr(S_TROWS)}, {sr(S_T0)}, {sr(S_TROWS)}")
+    a(f"s_sub_u32 {sr(S_T0)}, {sr(S_T0)}, {sr(S_TROWS)}")
+    a(f"s_cmp_ge_u32 {sr(S_T0)}, 64")              # (t > 64 ktiles wraps to a huge value)
     a(f"s_cbranch_scc1 {a.abort}")
     # --- which tile / k-piece: blocks [0, full) whole-K tiles, then the pieces
     l_piece, l_done = a.fresh("piece"), a.fresh("mapped")
@@ -177,15 +204,45 @@ def prologue(a: Asm):
     a(f"s_cselect_b32 {sr(S_TM)}, {sr(S_T0)}, {sr(S_Q)}")
     a(f"s_cselect_b32 {sr(S_TN)}, {sr(S_Q)}, {sr(S_T0)}")
 
-    # --- buffer resources: 64 rows x 256 columns from row k_begin, column 256 tm / tn
+    # --- buffer resources: 64 rows x 256 columns from row k_begin, column
+    # 256 tm / tn.  The workgroup that carries a T tail (T mod 64 != 0: a
+    # whole-K tile, or the last k-piece) takes its last tile as tile 0,
+    # through a window of its T mod 64 live rows, and starts tile 1 at k_begin
+    l_tail, l_rows = a.fresh("ktail"), a.fresh("krows")
     a(f"s_mul_i32 {sr(S_T3)}, {sr(S_S)}, {sr(S_KTP)}")
     a(f"s_lshl_b32 {sr(S_T3)}, {sr(S_T3)}, 6")         # k_begin (rows)
-    for srd_, base, ld, t, adv in ((SRD_A, S_A, S_LDA, S_TM, S_ADVA), (SRD_B, S_B, S_LDB, S_TN, S_ADVB)):
-        G.mul64(a, S_T0, S_T1, S_T3, ld)              # k_begin * ld
-        a(f"s_lshl_b32 {sr(S_T2)}, {sr(t)}, 9")       # 256 columns * 2 B
-        a(f"s_add_u32 {sr(S_T0)}, {sr(S_T0)}, {sr(S_T2)}")
+    a(f"s_mov_b32 {sr(S_ROW0)}, {sr(S_T3)}")
+    a(f"s_add_u32 {sr(S_ROW1)}, {sr(S_T3)}, 64")
+    a(f"s_mov_b32 {sr(S_ROWS0)}, 64")
+    a(f"s_and_b32 {sr(S_E0)}, {sr(S_TROWS)}, 63")      # SCC = (T mod 64 != 0)
+    a(f"s_cbranch_scc0 {l_rows}")
+    a(f"s_cmp_eq_u32 {sr(S_PIECE)}, 0")
+    a(f"s_cbranch_scc1 {l_tail}")
+    a(f"s_add_u32 {sr(S_E1)}, {sr(S_S)}, 1")
+    a(f"s_cmp_lg_u32 {sr(S_E1)}, {sr(S_SPLIT)}")
+    a(f"s_cbranch_scc1 {l_rows}")
+    a.label(l_tail)
+    a(f"s_sub_u32 {sr(S_E1)}, {sr(S_KTP)}, 1")
+    a(f"s_lshl_b32 {sr(S_E1)}, {sr(S_E1)}, 6")
+    a(f"s_add_u32 {sr(S_ROW0)}, {sr(S_T3)}, {sr(S_E1)}")
+    a(f"s_mov_b32 {sr(S_ROW1)}, {sr(S_T3)}")
+    a(f"s_mov_b32 {sr(S_ROWS0)}, {sr(S_E0)}")
+    a.label(l_rows)
+    a(f"s_sub_u32 {sr(S_ROWS0)}, {sr(S_ROWS0)}, 1")
+    for srd_, base, ld, t, adv, b1, nr in ((SRD_A, S_A, S_LDA, S_TM, S_ADVA, S_A1, S_NRA),
+                                          (SRD_B, S_B, S_LDB, S_TN, S_ADVB, S_B1, S_NRB)):
+        a(f"s_lshl_b32 {sr(S_E1)}, {sr(t)}, 9")       # 256 columns * 2 B
+        G.mul64(a, S_T0, S_T1, S_ROW1, ld)            # tile 1: its base, a 64-row window
+        a(f"s_add_u32 {sr(S_T0)}, {sr(S_T0)}, {sr(S_E1)}")
         a(f"s_addc_u32 {sr(S_T1)}, {sr(S_T1)}, 0")
-        a(f"s_mul_i32 {sr(S_T2)}, {sr(ld)}, 63")
+        a(f"s_add_u32 {sr(b1)}, {sr(base)}, {sr(S_T0)}")
+        a(f"s_addc_u32 {sr(b1 + 1)}, {sr(base + 1)}, {sr(S_T1)}")
+        a(f"s_mul_i32 {sr(nr)}, {sr(ld)}, 63")
+        a(f"s_add_u32 {sr(nr)}, {sr(nr)}, 512")
+        G.mul64(a, S_T0, S_T1, S_ROW0, ld)            # tile 0: (live rows - 1) ld + 512 bytes
+        a(f"s_add_u32 {sr(S_T0)}, {sr(S_T0)}, {sr(S_E1)}")
+        a(f"s_addc_u32 {sr(S_T1)}, {sr(S_T1)}, 0")
+        a(f"s_mul_i32 {sr(S_T2)}, {sr(ld)}, {sr(S_ROWS0)}")
         a(f"s_add_u32 {sr(S_T2)}, {sr(S_T2)}, 512")
         G.srd(a, srd_, base, S_T0, S_T1, S_T2)
         a(f"s_lshl_b32 {sr(adv)}, {sr(ld)}, 6")
@@ -320,6 +377,13 @@ def advance(half: str) -> list[str]:
     srd_ = SRD_A if half == "a" else SRD_B
     adv = S_ADVA if half == "a" else S_ADVB
     return [f"s_add_u32 {sr(srd_)}, {sr(srd_)}, {sr(adv)}", f"s_addc_u32 {sr(srd_ + 1)}, {sr(srd_ + 1)}, 0"]
+
+
+def to_tile1(half: str) -> list[str]:
+    """After tile 0's DMA: the 64-row window at the workgroup's tile 1."""
+    srd_, b1, nr = (SRD_A, S_A1, S_NRA) if half == "a" else (SRD_B, S_B1, S_NRB)
+    return [f"s_mov_b32 {sr(srd_)}, {sr(b1)}", f"s_mov_b32 {sr(srd_ + 1)}, {sr(b1 + 1)}",
+            f"s_mov_b32 {sr(srd_ + 2)}, {sr(nr)}"]
 
 
 def frag_reads(kind: str, f: int, sub: int) -> list[str]:
@@ -495,7 +559,7 @@ def kernel(variant: str = "") -> tuple[str, str]:
     prologue(a)
     for half in ("a", "b"):                     # tile 0 -> stage 0
         prologue_dma(a, half)
-        for ins in advance(half):
+        for ins in to_tile1(half):
             a(ins)
     a(f"s_xor_b32 {sr(S_M0A)}, {sr(S_M0A)}, {sr(S_M0AT)}")
     a(f"s_xor_b32 {sr(S_M0B)}, {sr(S_M0B)}, {sr(S_M0BT)}")

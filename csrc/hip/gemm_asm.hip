@@ -12,12 +12,19 @@
 //   toa_gemm_asm_swiglu_bwd   dgu = SwiGLU'(gu) applied to ds = dY WdT^T
 //                             (ds never stored)                  (one launch)
 //
-// Shapes: M, N multiples of 256 (F of 128 forward / 256 backward), K a
+// Shapes: N a multiple of 256 (F of 128 forward / 256 backward), K a
 // multiple of 64 and >= 128, row strides multiples of 8 elements, 16-byte
-// aligned bases.  Anything else returns hipErrorInvalidValue before a launch
-// (callers fall back to another GEMM), so the kernel never sees a shape whose
-// tiles it does not cover.  The 80-byte argument block matches KARG in
-// gemm_gen.py (and csrc/asm/host_args.py, which the CPU emulator tests use).
+// aligned bases.  M (the token count) is free for the product launchers
+// toa_gemm_asm_rows / _resadd / _swiglu / _swiglu_bwd: tiles_m = ceil(M /
+// 256) and the kernarg word `m` ends the last tile row's X / C / S resources
+// at row M, so the hardware's range check zero-fills its loads and drops its
+// stores past M.  Every other entry (toa_gemm_asm itself, whose refusal of a
+// partial tile row callers and tests rely on, the variant, timing, trace,
+// probe, persistent arms, the rope and delta epilogues) takes M % 256 == 0.
+// Anything else returns hipErrorInvalidValue before a launch (callers fall
+// back to another GEMM), so the kernel never sees a shape whose tiles it does
+// not cover.  The 96-byte argument block matches KARG in gemm_gen.py (and
+// csrc/asm/host_args.py, which the CPU emulator tests use).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -104,7 +111,7 @@ struct __attribute__((packed)) Args {
   uint32_t map;     // tile order: log2 group | 16 = column groups walk the rows (gemm_gen.py KARG)
   uint32_t grid;    // persistent kernels: the workgroup count
   uint32_t phase;   // first-wave start offsets: n | log2 g << 16 (gemm_gen.py phase_delay; 0 = off)
-  uint32_t pad;
+  uint32_t m;       // rows of X / C when M % 256 != 0 (0 = tiles_m whole tiles; the delta kernel: pointer bytes)
 };
 static_assert(sizeof(Args) == 96, "kernarg block must match csrc/asm/gemm_gen.py KARG_BYTES");
 
@@ -191,7 +198,8 @@ Args base_args(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, 
   a.ldw = (uint32_t)(ldw * 2);
   a.ldc = (uint32_t)(ldc * 2);
   a.ktiles = (uint32_t)(K / 64);
-  a.tiles_m = (uint32_t)(M / 256);
+  a.tiles_m = (uint32_t)((M + 255) / 256);
+  a.m = M % 256 ? (uint32_t)M : 0u;
   a.tiles_n = (uint32_t)tiles_n;
   const uint32_t nwg = a.tiles_m * a.tiles_n;
   a.xq = nwg >> 3;
@@ -201,9 +209,10 @@ Args base_args(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, 
   return a;
 }
 
-bool common_ok(int M, int K, int64_t ldx, int64_t ldw, const void* X, const void* W) {
-  return M > 0 && M % 256 == 0 && K >= 128 && K % 64 == 0 && ld_ok(ldx, K) && ld_ok(ldw, K) && al16(X) && al16(W) &&
-         (int64_t)(M / 256) < (1 << 20);
+// m_tail: the launcher takes any M (the product launchers; see the header).
+bool common_ok(int M, int K, int64_t ldx, int64_t ldw, const void* X, const void* W, bool m_tail = false) {
+  return M > 0 && (m_tail || M % 256 == 0) && K >= 128 && K % 64 == 0 && ld_ok(ldx, K) && ld_ok(ldw, K) && al16(X) &&
+         al16(W) && (int64_t)M < (1 << 28);
 }
 
 }  // namespace
@@ -248,16 +257,29 @@ bool use_persist(int N, int K) {
   return g_persist == 1 && K <= 6144 && N <= 6144;
 }
 
-extern "C" int toa_gemm_asm(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc, int M,
-                            int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C))
+static int gemm_asm_plain(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc, int M,
+                          int N, int K, bool m_tail, hipStream_t stream) {
+  if (!common_ok(M, K, ldx, ldw, X, W, m_tail) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
-  if (use_persist(N, K)) {
+  if (M % 256 == 0 && use_persist(N, K)) {
     const unsigned tiles = a.tiles_m * a.tiles_n;
     return launch(kVariantFn[2], a, stream, tiles < kPersistGrid ? tiles : kPersistGrid);
   }
   return launch(K_PLAIN, a, stream);
+}
+
+extern "C" int toa_gemm_asm(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc, int M,
+                            int N, int K, hipStream_t stream) {
+  return gemm_asm_plain(X, ldx, W, ldw, C, ldc, M, N, K, false, stream);
+}
+
+// toa_gemm_asm for any row count M >= 1 (the same kernel and, at M % 256 ==
+// 0, the same launch): the rows of the last tile row past M are cut by the
+// buffer resources (gemm_gen.py KARG "m").
+extern "C" int toa_gemm_asm_rows(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc,
+                                 int M, int N, int K, hipStream_t stream) {
+  return gemm_asm_plain(X, ldx, W, ldw, C, ldc, M, N, K, true, stream);
 }
 
 extern "C" int toa_gemm_asm_set_persist(int v) {
@@ -420,6 +442,35 @@ extern "C" int toa_wgrad_asm_set_map(int map) {
   return 0;
 }
 
+// The auto plan's split.  K (the token count) a multiple of 64: wgrad.hip's
+// plan, shared with the HIP kernel.  Any other K (this kernel only: ceil(K /
+// 64) k-tiles, the last one staged through resources that end at row K, so
+// its rows past K read as 0): the largest split in 2..4 that fills the
+// last wave, DIVIDES the k-tiles -- pieces are cut at multiples of 64 rows, the
+// last one carries the tail -- and leaves 512 rows a piece (wgrad.hip's floor).
+// Mirrored by csrc/asm/host_args.py wgrad_plan.
+static int wgrad_asm_split(int M, int N, int K) {
+  if (K % 64 == 0) return toa_wgrad_split(M, N, K);
+  const int rem = ((M / 256) * (N / 256)) % 256, kt = (K + 63) / 64;
+  int best = 1;
+  for (int s = 2; rem && s <= 4; ++s)
+    if (rem * s <= 256 && kt % s == 0 && K / s >= 512) best = s;
+  return best;
+}
+
+// Bytes of fp32 workspace toa_wgrad_asm needs (toa_wgrad_workspace's contract
+// on this kernel's plan; equal to it wherever K % 64 == 0).
+extern "C" int64_t toa_wgrad_asm_workspace(int M, int N, int K, int split) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || split < 0) return 0;
+  const int64_t tiles = (int64_t)(M / 256) * (N / 256);
+  int64_t rem = tiles;
+  if (split == 0) {
+    split = wgrad_asm_split(M, N, K);
+    rem = tiles % 256;
+  }
+  return split > 1 ? (int64_t)split * rem * 256 * 256 * 4 : 0;
+}
+
 extern "C" int toa_wgrad_asm(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C, int64_t ldc,
                              float* W, int M, int N, int K, int split, int beta, hipStream_t stream) {
   return wgrad_asm_launch(K_WGRAD, A, lda, B, ldb, C, ldc, W, M, N, K, split, beta, stream);
@@ -441,15 +492,16 @@ static int wgrad_asm_launch(int which, const bf16_t* A, int64_t lda, const bf16_
       (ldb * 2) * 64 >= (1ll << 31))
     return (int)hipErrorInvalidValue;
   const int tiles = (M / 256) * (N / 256);
+  const int kt = (K + 63) / 64;   // k-tiles; K % 64 rows of the last one are live when K % 64 != 0
   int full;
   if (split == 0) {
-    split = toa_wgrad_split(M, N, K);
+    split = wgrad_asm_split(M, N, K);
     full = split > 1 ? tiles - tiles % 256 : tiles;
   } else {
     full = split == 1 ? tiles : 0;
   }
   const int rem = tiles - full;
-  if (K % (64 * split) || K / split < 128 || (split > 1 && (W == nullptr || !al16(W))) ||
+  if (kt % split || kt / split < 2 || (split > 1 && (W == nullptr || !al16(W))) ||
       (int64_t)split * rem >= (1 << 14))
     return (int)hipErrorInvalidValue;
   Args a;
@@ -462,7 +514,8 @@ static int wgrad_asm_launch(int which, const bf16_t* A, int64_t lda, const bf16_
   a.ldw = (uint32_t)(ldb * 2);
   a.ldc = (uint32_t)(ldc * 2);
   a.lds = (uint32_t)(beta ? 1 : 0);
-  a.ktiles = (uint32_t)(K / 64);
+  a.ktiles = (uint32_t)kt;
+  a.fw = K % 64 ? (uint32_t)K : 0u;   // wgrad_gen.py KARG "t" (0 = 64 ktiles rows)
   a.tiles_m = (uint32_t)(M / 256);
   a.tiles_n = (uint32_t)(N / 256);
   a.xq = (uint32_t)full;
@@ -594,7 +647,7 @@ extern "C" int toa_gemm_asm_set_swiglu_persist(int v) {
   return 0;
 }
 static int launch_swiglu(int which, int persist_bit, const Args& a, hipStream_t stream) {
-  if (!g_epi_r4 && (swiglu_persist() & persist_bit)) {
+  if (!g_epi_r4 && a.m == 0 && (swiglu_persist() & persist_bit)) {   // (the persistent arms: whole tiles only)
     const unsigned tiles = a.tiles_m * a.tiles_n;
     return launch(which == K_SWIGLU_FWD ? K_SWFWD_P1 : K_SWBWD_P1, a, stream,
                   tiles < kPersistGrid ? tiles : kPersistGrid);
@@ -604,7 +657,7 @@ static int launch_swiglu(int which, int persist_bit, const Args& a, hipStream_t 
 
 extern "C" int toa_gemm_asm_swiglu(const bf16_t* X, int64_t ldx, const bf16_t* Wgu, int64_t ldw, bf16_t* GU,
                                    int64_t ldgu, bf16_t* S, int64_t lds_, int M, int F, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, Wgu) || F <= 0 || F % 128 || !ld_ok(ldgu, 2 * F) || !ld_ok(lds_, F) || !al16(GU) ||
+  if (!common_ok(M, K, ldx, ldw, X, Wgu, true) || F <= 0 || F % 128 || !ld_ok(ldgu, 2 * F) || !ld_ok(lds_, F) || !al16(GU) ||
       !al16(S) || (int64_t)F * ldw * 2 + 128 * ldw * 2 >= (1ll << 32))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, Wgu, ldw, GU, ldgu, M, F / 128, K);
@@ -612,20 +665,20 @@ extern "C" int toa_gemm_asm_swiglu(const bf16_t* X, int64_t ldx, const bf16_t* W
   a.lds = (uint32_t)(lds_ * 2);
   a.fw = (uint32_t)((int64_t)F * ldw * 2);
   a.fc = (uint32_t)(F * 2);
-  return g_epi_r4 ? launch(K_SWIGLU_FWD_R4, a, stream) : launch_swiglu(K_SWIGLU_FWD, 1, a, stream);
+  return g_epi_r4 && a.m == 0 ? launch(K_SWIGLU_FWD_R4, a, stream) : launch_swiglu(K_SWIGLU_FWD, 1, a, stream);
 }
 
 extern "C" int toa_gemm_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16_t* WdT, int64_t ldw,
                                        const bf16_t* GU, int64_t ldgu, bf16_t* dGU, int64_t lddgu, int M, int F, int K,
                                        hipStream_t stream) {
-  if (!common_ok(M, K, ldy, ldw, dY, WdT) || F <= 0 || F % 256 || !ld_ok(ldgu, 2 * F) || !ld_ok(lddgu, 2 * F) ||
+  if (!common_ok(M, K, ldy, ldw, dY, WdT, true) || F <= 0 || F % 256 || !ld_ok(ldgu, 2 * F) || !ld_ok(lddgu, 2 * F) ||
       !al16(GU) || !al16(dGU))
     return (int)hipErrorInvalidValue;
   Args a = base_args(dY, ldy, WdT, ldw, dGU, lddgu, M, F / 256, K);
   a.S = (uint64_t)GU;
   a.lds = (uint32_t)(ldgu * 2);
   a.fc = (uint32_t)(F * 2);
-  return g_epi_r4 ? launch(K_SWIGLU_BWD_R4, a, stream) : launch_swiglu(K_SWIGLU_BWD, 2, a, stream);
+  return g_epi_r4 && a.m == 0 ? launch(K_SWIGLU_BWD_R4, a, stream) : launch_swiglu(K_SWIGLU_BWD, 2, a, stream);
 }
 
 // The fused-QKV projection x Wqkv^T written as RoPE-rotated, head-major
@@ -667,7 +720,7 @@ extern "C" int toa_gemm_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t* W,
 // C = X W^T + R, R bf16 laid out like C (gemm_gen.py epilogue_resadd).
 extern "C" int toa_gemm_asm_resadd(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc,
                                    const bf16_t* R, int M, int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !al16(R))
+  if (!common_ok(M, K, ldx, ldw, X, W, true) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !al16(R))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)R;

@@ -103,6 +103,7 @@ _SIGS = {
     "toa_gemm_set_no_streamk": [c_int],
     "toa_gemm_prewarm": [],
     "toa_gemm_asm": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
+    "toa_gemm_asm_rows": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_swiglu_bwd": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_swiglu_bwd_variant": [c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
@@ -176,6 +177,9 @@ def _load():
         ww = getattr(lib, "toa_wgrad_workspace", None)
         if ww is not None:
             ww.argtypes, ww.restype = [c_int, c_int, c_int, c_int], c_i64
+        wa = getattr(lib, "toa_wgrad_asm_workspace", None)
+        if wa is not None:
+            wa.argtypes, wa.restype = [c_int, c_int, c_int, c_int], c_i64
         _lib = lib
 
 
@@ -201,7 +205,8 @@ def has(name: str) -> bool:
 
 
 # launchers whose argument / result types _load sets outside _SIGS
-_TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coherent_alloc", "toa_wgrad_workspace"}
+_TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coherent_alloc", "toa_wgrad_workspace",
+                    "toa_wgrad_asm_workspace"}
 
 
 def _fn(name: str):

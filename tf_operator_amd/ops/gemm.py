@@ -240,8 +240,12 @@ def _why_not_asm(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> str:
     N = w.shape[0]
     if x2.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         return f"dtype {x2.dtype}/{w.dtype}, not bf16"
-    if M % 256 or N % n_mult:
-        return f"M={M} / N={N} not multiples of 256 (tokens per micro-batch x seq, output features)"
+    if not 0 < M < 1 << 28:
+        return f"M={M} (tokens per micro-batch x seq) outside 1 .. 2^28 - 1"
+    if M % 256 and _MODE != "asm":
+        return f"M={M} not a multiple of 256 outside the asm policy (first_step takes whole tiles only)"
+    if N % n_mult:
+        return f"N={N} (output features) not a multiple of {n_mult}; only the token count M is free"
     if K % 64 or K < 128:
         return f"K={K} not a multiple of 64 >= 128"
     return "layout: non-unit column stride, unaligned rows or base"
@@ -278,9 +282,12 @@ def asm_takes(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> bool:
     csrc/hip/gemm_asm.hip (``common_ok`` / ``ld_ok`` / ``al16``, which refuse
     anything else) on x2 [M, K] and w [N, K].  bf16 GPU rows with unit column
     stride, 16-byte aligned bases, row strides >= K, multiples of 8 and under
-    2^23 elements, M and N multiples of 256 (n_mult), M < 2^28, K a multiple
-    of 64 and >= 128.  The fused epilogues' predicates (ops/llm.py) build on
-    it and add only what their own launcher checks."""
+    2^23 elements, any 0 < M < 2^28 (the token count: the last tile row's
+    tail is cut by the kernels' buffer resources, docs/kernels.md; under
+    first_step, a hipBLASLt policy's start-up, multiples of 256 only as
+    before), N a multiple of 256 (n_mult), K a multiple of 64 and >= 128.  The fused
+    epilogues' predicates (ops/llm.py) build on it and add only what their
+    own launcher checks -- the RoPE and delta epilogues their S % 256 == 0."""
     if not (_MODE == "asm" or _asm_first) or not _lib.has("toa_gemm_asm"):
         return False
     if not (x2.is_cuda and x2.dtype == w.dtype == torch.bfloat16 and x2.dim() == 2 and w.dim() == 2):
@@ -290,7 +297,9 @@ def asm_takes(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> bool:
     for t in (x2, w):
         if t.stride(1) != 1 or t.stride(0) < K or t.stride(0) % 8 or t.stride(0) >= 1 << 23 or t.data_ptr() % 16:
             return False
-    return (0 < M < 1 << 28 and M % 256 == 0 and N > 0 and N % n_mult == 0 and K % 64 == 0 and K >= 128
+    if M % 256 and not (_MODE == "asm" and _lib.has("toa_gemm_asm_rows")):
+        return False
+    return (0 < M < 1 << 28 and N > 0 and N % n_mult == 0 and K % 64 == 0 and K >= 128
             and w.shape[1] == K and _lib.use_hip(x2))
 
 
@@ -298,8 +307,9 @@ def linear_fwd(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     if asm_takes(x2, w):
         M, N = x2.shape[0], w.shape[0]
         y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
-        _lib.call("toa_gemm_asm", _lib.ptr(x2), x2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(y), N, M, N,
-                  x2.shape[1], _lib.stream(x2))
+        # (toa_gemm_asm itself refuses a partial last tile row; same kernel)
+        _lib.call("toa_gemm_asm_rows" if M % 256 else "toa_gemm_asm", _lib.ptr(x2), x2.stride(0), _lib.ptr(w),
+                  w.stride(0), _lib.ptr(y), N, M, N, x2.shape[1], _lib.stream(x2))
         return y
     lib_ok = _ok(x2, w)
     if _MODE == "asm" and x2.is_cuda and x2.dim() == 2 and w.dim() == 2:
@@ -413,9 +423,24 @@ def _workspace(dev, nbytes):
     return t
 
 
+def _hip_wgrad_takes_tokens(T: int) -> bool:
+    """Token counts csrc/hip/wgrad.hip takes (its plan and its k-loop)."""
+    return T % 128 == 0 and T >= 1024
+
+
+def _asm_wgrad_takes_tokens(T: int) -> bool:
+    """Token counts the assembly kernel takes when it is the selected one
+    (csrc/hip/gemm_asm.hip wgrad_asm_launch): any T >= 65 -- ceil(T / 64) >= 2
+    k-tiles, the last one's rows past T read as 0 through the operands'
+    buffer resources."""
+    return wgrad_kernel() in ("asm", "asm_v1") and _lib.has("toa_wgrad_asm_workspace") and T >= 65
+
+
 def wgrad_hip_ok(g, dy2, x2) -> bool:
-    """Shapes/layouts csrc/hip/wgrad.hip takes: bf16, 256-multiple output
-    dims, token count a multiple of 64, unit column stride."""
+    """Shapes/layouts the hand-written weight-gradient kernels take: bf16,
+    256-multiple output dims, unit column stride, and a token count either
+    kernel takes -- csrc/hip/wgrad.hip multiples of 128 from 1024, the
+    assembly kernel (when selected) any T >= 65."""
     if not _lib.has("toa_wgrad"):
         return False
     if not (dy2.is_cuda and g.dtype == dy2.dtype == x2.dtype == torch.bfloat16 and g.is_contiguous()):
@@ -424,7 +449,8 @@ def wgrad_hip_ok(g, dy2, x2) -> bool:
         return False
     T, N = dy2.shape
     K = x2.shape[1]
-    return (N % 256 == 0 and K % 256 == 0 and T % 128 == 0 and T >= 1024 and dy2.stride(0) % 8 == 0
+    tokens_ok = _hip_wgrad_takes_tokens(T) or _asm_wgrad_takes_tokens(T)
+    return (N % 256 == 0 and K % 256 == 0 and tokens_ok and dy2.stride(0) % 8 == 0
             and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0
             and g.data_ptr() % 16 == 0 and tuple(g.shape) == (N, K))
 
@@ -531,13 +557,19 @@ def wgrad_hip_(g, dy2, x2, beta=1.0, split=None):
     T, N = dy2.shape
     K = x2.shape[1]
     split = 0 if split is None else int(split)
-    nbytes = int(_lib.call_ret("toa_wgrad_workspace", N, K, T, split))
+    # a token count only the assembly kernel takes: its own plan (the split
+    # divides the ceil(T / 64) k-tiles), and never the HIP kernel below
+    hip_takes = _hip_wgrad_takes_tokens(T)
+    nbytes = int(_lib.call_ret("toa_wgrad_workspace" if hip_takes else "toa_wgrad_asm_workspace", N, K, T, split))
     ws = _workspace(dy2.device, nbytes) if nbytes > 0 else None
     args = (_lib.ptr(dy2), dy2.stride(0), _lib.ptr(x2), x2.stride(0), _lib.ptr(g), K, _lib.ptr(ws),
             N, K, T, int(split), int(beta != 0.0), _lib.stream(dy2))
     kern = wgrad_kernel()
     if kern in ("asm", "asm_v1"):
-        sess = _session_for(g) if _SESSIONS else None
+        # the gradient-norm partials stay on the token counts they were
+        # measured at (both kernels' common ones); elsewhere the optimizer's
+        # full pass over the gradient gives the clipping norm
+        sess = _session_for(g) if _SESSIONS and hip_takes else None
         armed = sess is not None and sess.arm(g)
         try:
             rc = (_lib.call_ret("toa_wgrad_asm", *args) if kern == "asm"
@@ -553,6 +585,10 @@ def wgrad_hip_(g, dy2, x2, beta=1.0, split=None):
             raise RuntimeError(f"toa_wgrad_asm failed: hipError {rc}")
         # a shape / layout the assembly kernel's launcher refuses (it checks
         # before launching): the HIP kernel shares its split plan and reduce
+    if not hip_takes:
+        raise RuntimeError(f"weight gradient {N}x{K}x{T}: T={T} is a token count only the assembly kernel takes "
+                           f"(csrc/hip/wgrad.hip: T % 128 == 0, T >= 1024) and it "
+                           + ("refused the operands" if kern in ("asm", "asm_v1") else f"is not selected ({kern})"))
     _lib.call("toa_wgrad", *args)
     return g
 
@@ -564,7 +600,9 @@ def wgrad_acc_(g: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor, beta: float
     if dy2.is_cuda and g.dtype == torch.bfloat16 and dy2.dim() == 2 and x2.dim() == 2:
         T, N = dy2.shape
         _fallback("wgrad", (N, x2.shape[1], T), "hipBLASLt" if _ok(dy2, x2) else "torch.mm",
-                  "output dims not multiples of 256, tokens not a multiple of 128 (>= 1024), or layout")
+                  "output dims not multiples of 256, layout, or tokens: "
+                  + ("under 65" if wgrad_kernel() in ("asm", "asm_v1")
+                     else "not a multiple of 128 (>= 1024) for the HIP kernel (TOA_WGRAD=hip)"))
     if (g.dtype == torch.float32 and dy2.dtype == x2.dtype == torch.bfloat16 and g.is_cuda and g.is_contiguous()
             and dy2.stride(1) == 1 and x2.stride(1) == 1 and _lib.has("toa_gemm")):
         # fp32 master-gradient accumulation (small payloads): one hipBLASLt call

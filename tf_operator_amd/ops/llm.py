@@ -224,7 +224,7 @@ def _resadd_ok(a2, w, residual, M) -> bool:
     """gemm.linear_resadd takes out [M, N] = a w^T + residual: operands the
     assembly GEMM takes (a2 has a's row layout) and a bf16, contiguous,
     16-byte aligned residual of the output's size."""
-    return (gemm.mode() == "asm" and gemm.asm_takes(a2, w) and 0 < M < 1 << 28 and M % 256 == 0
+    return (gemm.mode() == "asm" and gemm.asm_takes(a2, w) and 0 < M < 1 << 28
             and residual.dtype == torch.bfloat16 and residual.is_contiguous() and residual.data_ptr() % 16 == 0
             and residual.numel() == M * w.shape[0] and _lib.has("toa_gemm_asm_resadd") and resadd_fused_enabled())
 

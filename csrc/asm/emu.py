@@ -90,6 +90,7 @@ class Wave:
         self.scc = 0
         self.m0 = 0
         self.vcc = 0
+        self.exec = (1 << 64) - 1     # honoured by v_accvgpr_read_b32 (the NN epilogues' lane swap); Emu.step refuses the rest
         self.pc = 0
         self.done = False
         self.wid = wid
@@ -234,6 +235,11 @@ class Emu:
         h = getattr(self, "op_" + op, None)
         if h is None:
             raise NotImplementedError(op)
+        # EXEC masking is implemented for v_accvgpr_read_b32 alone: anything else that acts per lane
+        # under a partial mask would be emulated full-width, so it is refused
+        if w.exec != (1 << 64) - 1 and op.startswith(("v_", "ds_", "buffer_", "global_")) \
+                and op != "v_accvgpr_read_b32":
+            raise NotImplementedError(f"{op} under a partial EXEC mask")
         return h(w, args, mods)
 
     # ------------------------------------------------------------ SALU
@@ -523,6 +529,8 @@ class Emu:
     def _mask(self, w, tok) -> np.ndarray:
         if tok == "vcc":
             v = w.vcc
+        elif tok == "exec":
+            v = w.exec
         else:
             kind, lo, hi = self._reg(w, tok)
             v = (int(w.s[lo]) & M32) | ((int(w.s[lo + 1]) & M32) << 32)
@@ -532,6 +540,8 @@ class Emu:
         v = int(sum(1 << l for l in range(64) if bits[l]))
         if tok == "vcc":
             w.vcc = v
+        elif tok == "exec":
+            w.exec = v
         else:
             kind, lo, hi = self._reg(w, tok)
             w.s[lo], w.s[lo + 1] = v & M32, v >> 32
@@ -610,7 +620,9 @@ class Emu:
         self.vset(w, a[0], self.vget(w, a[1]))
 
     def op_v_accvgpr_read_b32(self, w, a, m):
-        self.vset(w, a[0], self.vget(w, a[1]))
+        """EXEC-masked: inactive lanes keep their destination."""
+        on = self._mask(w, "exec")
+        self.vset(w, a[0], np.where(on, self.vget(w, a[1]), self.vget(w, a[0])))
 
     def op_v_cvt_pk_bf16_f32(self, w, a, m):
         lo = bf16_rne(u2f(self.vget(w, a[1])))

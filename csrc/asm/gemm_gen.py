@@ -124,6 +124,7 @@ S_ITER, S_GRID = 90, 91   # persistent arms: this workgroup's tile-order index, 
 SRD_D, S_DOFF, S_DSTEP = 72, 76, 77
 S_MAP, S_KGRID = 92, 93   # kernarg map / grid words (s94, s95: the map's decoded log2 group, walk flag)
 S_LG, S_WALK = 94, 95
+S_ADVW = 78         # NN kernels: 64 rows of W in bytes (the window's step per k-tile)
 N_SGPR = 96
 
 # VGPRs
@@ -310,8 +311,10 @@ def phase_delay(a: Asm):
     a.label(l_done)
 
 
-def tile_setup(a: Asm, epi: str, bid: str = "s2"):
-    """Tile of block `bid` -> S_TILE, (S_TM, S_TN), SRD_X / SRD_W."""
+def tile_setup(a: Asm, epi: str, bid: str = "s2", form: str = "tn"):
+    """Tile of block `bid` -> S_TILE, (S_TM, S_TN), SRD_X / SRD_W.  form "nn":
+    W is [K, N] as stored, its resource the 64-row window of k-tile 0 at
+    column 256 tn (the NN kernels below)."""
     # --- XCD remap: blocks b, b+8, ... share an XCD; give each XCD a
     # contiguous range of the tile order (bijective for any nwg)
     a(f"s_and_b32 {sr(S_T0)}, {bid}, 7")              # xcd
@@ -350,6 +353,16 @@ def tile_setup(a: Asm, epi: str, bid: str = "s2"):
     mul64(a, S_T2, S_T3, S_T0, S_LDX)
     tile_rows_bytes(a, S_T1, S_LDX)
     srd(a, SRD_X, S_X, S_T2, S_T3, S_T1)
+    if form == "nn":
+        # W: rows 0..63, columns tn*256 .. +255: 63 row strides + 512 B, so the
+        # last window ends with W's row K - 1 (it advances 64 rows per k-tile)
+        a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, 9")
+        a(f"s_mul_i32 {sr(S_T1)}, {sr(S_LDW)}, 63")
+        a(f"s_add_u32 {sr(S_T1)}, {sr(S_T1)}, 512")
+        a(f"s_mov_b32 {sr(S_T3)}, 0")
+        srd(a, SRD_W, S_W, S_T0, S_T3, S_T1)
+        a(f"s_lshl_b32 {sr(S_ADVW)}, {sr(S_LDW)}, 6")
+        return
     # W: rows tn*256 (tn*128 for the gate|up projection)
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, {7 if epi == 'swiglu_fwd' else 8}")
     mul64(a, S_T2, S_T3, S_T0, S_LDW)
@@ -402,11 +415,13 @@ def tile_c(a: Asm, epi: str):
 
 
 
-def prologue(a: Asm, epi: str):
+def prologue(a: Asm, epi: str, form: str = "tn"):
     prologue_args(a, epi)
-    tile_setup(a, epi, sr(S_ITER) if SCHED["persist"] else "s2")
+    tile_setup(a, epi, sr(S_ITER) if SCHED["persist"] else "s2", form)
     tile_c(a, epi)
     prologue_lanes(a, epi)
+    if form == "nn":
+        nn_lanes(a)
 
 
 def prologue_lanes(a: Asm, epi: str):
@@ -1264,13 +1279,24 @@ def unpack_bf16(a: Asm, dst: int, src: int):
 
 
 LOG2E = 1.4426950408889634
+NN_SWAP = False                 # set while an NN kernel is generated (kernel_nn)
+S_EX_SAME, S_EX_SWAP = 84, 86   # NN epilogues: EXEC masks of the lanes whose fragment pairs are in / out of column order
 
 
 def read_pair(a: Asm, dst: int, p: int, j: int, ioff: int = 0):
     """dst[0..7] = the lane's 8 consecutive columns of fragments (2p, j) and
-    (2p+1, j) (ioff: fragment offset, 4 for SwiGLU's up half)."""
+    (2p+1, j) (ioff: fragment offset, 4 for SwiGLU's up half).  In the NN
+    kernels (NN_SWAP) lane groups 1 and 2 hold the pair's two fragments the
+    other way round: two EXEC-masked passes put them in column order."""
+    if NN_SWAP:
+        a(f"s_mov_b64 exec, {sr(S_EX_SAME, 2)}")        # lanes 0..15, 48..63
     read_acc4(a, dst, acc_index(2 * p + ioff, j))
     read_acc4(a, dst + 4, acc_index(2 * p + 1 + ioff, j))
+    if NN_SWAP:
+        a(f"s_mov_b64 exec, {sr(S_EX_SWAP, 2)}")        # lanes 16..47
+        read_acc4(a, dst + 4, acc_index(2 * p + ioff, j))
+        read_acc4(a, dst, acc_index(2 * p + 1 + ioff, j))
+        a("s_mov_b64 exec, -1")
 
 
 def cvt_pack8(a: Asm, dst: int, src: int):
@@ -1780,6 +1806,261 @@ def persistent_next(a: Asm, epi: str, l_tile: str):
     a.label(l_last)
 
 
+# ---------------------------------------------------------------- NN form
+# C[m][n] = sum_k X[m][k] * W[k][n]: the data gradient dX = dY W read from the
+# weight AS STORED ([K = out features, N = in features], row stride ldw), so
+# no transposed copy of W is kept.  The TN kernel's X half (lines, LDS-DMA,
+# ds_read_b128) plus the weight-gradient kernel's operand image for W
+# (wgrad_gen: a 64 (k) x 256 (n) window per k-tile, row pairs as one-DMA
+# blocks at blockbase, fragments through ds_read_b64_tr_b16 from two base
+# VGPRs, rows +0 and +4).  A lane's W fragment holds k = 32 sub + 8 (l >> 4)
+# .. +7 (two transposed reads), the k of its X fragment's ds_read_b128.
+#
+# The accumulators keep the TN kernels' shape (fragments 2p and 2p + 1 give a
+# lane the 8 consecutive columns of one 16-byte chunk), so every epilogue
+# applies: source lane (g, q, p) = (l >> 4, (l >> 2) & 3, l & 3) of fragment i
+# reads row 8 g + q, chunk 4 (i >> 1) + p of the wave's 16, and of that chunk
+# the 8-byte half (i & 1) ^ par(p), par(p) = (p & 1) ^ (p >> 1).  Were the
+# half i & 1 in every lane (TN's layout exactly), the 32 lanes of a read would
+# reach only every other pair of banks (chunks sit on 16-byte boundaries: the
+# LDS-DMA places 16 bytes per lane): 2-way conflicts.  With par the four
+# pieces of a row fall at 0, 24, 72, 80 (mod 32: 0, 24, 8, 16) and the eight
+# rows of a read group at multiples of 32 mod 256: every bank once, 2 LDS
+# cycles per read (tests/test_asm_gemm_nn.py).  The price: in lane groups 1
+# and 2 (par = 1) fragment 2p holds the chunk's upper half and 2p + 1 its
+# lower; read_pair puts them in order with two EXEC-masked passes of
+# v_accvgpr_read (256 more per tile), the only change to the epilogues.  The
+# half is part of the read base, so odd fragments have bases of their own.
+#
+# LDS per stage: X half (HALF) + W image (wgrad_gen.OPER) = 72640 B, two
+# stages 145280 B, the delta epilogue's 1 KiB behind them.
+NN_EPIS = ("plain", "swiglu_bwd", "delta")
+NN_MAP = "lib0"
+# W read bases and stage toggles beside V_RW / V_RWT (even fragments, rows +0): rows +4, and both for the odd
+# fragments (main loop only: epilogue scratch)
+V_RWH, V_RWHT, V_RWO, V_RWOT, V_RWHO, V_RWHOT = (V_E + k for k in range(4, 10))
+NN_BASES = ((V_RW, V_RWT), (V_RWH, V_RWHT), (V_RWO, V_RWOT), (V_RWHO, V_RWHOT))
+
+
+def _wgrad():
+    import wgrad_gen   # lazy: it imports this module
+    return wgrad_gen
+
+
+def nn_layout() -> tuple[int, int]:
+    """(bytes per stage, LDS bytes of the two stages) of the NN kernels."""
+    stage = HALF + _wgrad().OPER
+    return stage, 2 * stage
+
+
+def nn_frag_offset(i: int, sub: int) -> int:
+    """Immediate of W fragment i, sub-step `sub`, from the lane's read base
+    (of its parity: the chunk's half is in the base)."""
+    wg = _wgrad()
+    return wg.pos(0, 4 * (i >> 1)) + wg.SUB1 * sub
+
+
+def nn_lanes(a: Asm):
+    """The W side's lane state after prologue_lanes (V_T = w, V_T + 1 = lane
+    still hold; its TN values of these registers are replaced): V_DW, the
+    piece offsets, the M0 bases, the two read bases and their toggles."""
+    wg = _wgrad()
+    stage, _ = nn_layout()
+    v = V_T
+    # DMA: wave w's piece j is block 8 w + j of the window (rows 16 w + 2 j + s)
+    wg.dma_lane(a, v, V_E)
+    a(f"v_mul_lo_u32 {vr(V_DW)}, {vr(v + 2)}, {sr(S_LDW)}")
+    a(f"v_add_u32 {vr(V_DW)}, {vr(V_DW)}, {vr(v + 3)}")
+    for j in range(1, 8):
+        a(f"s_mul_i32 {sr(S_SOW + j - 1)}, {sr(S_LDW)}, {2 * j}")
+    a("s_nop 4")
+    a(f"v_readfirstlane_b32 {sr(S_T0)}, {vr(v)}")              # w
+    a("s_nop 4")
+    a(f"s_mul_i32 {sr(S_M0W)}, {sr(S_T0)}, {wg.blockbase(8)}")
+    a(f"s_add_u32 {sr(S_M0W)}, {sr(S_M0W)}, {HALF}")
+    a(f"s_add_u32 {sr(S_M0WT)}, {sr(S_M0W)}, {stage}")
+    a(f"s_xor_b32 {sr(S_M0WT)}, {sr(S_M0WT)}, {sr(S_M0W)}")
+    # read bases: pos(8 g + q, p) + the wave's 128 columns, rows +4 two blocks on
+    a(f"v_lshrrev_b32 {vr(v + 2)}, 4, {vr(v + 1)}")                 # g
+    a(f"v_bfe_u32 {vr(v + 3)}, {vr(v + 1)}, 3, 1")                  # q >> 1
+    a(f"v_lshl_add_u32 {vr(v + 2)}, {vr(v + 2)}, 2, {vr(v + 3)}")   # block 4 g + (q >> 1)
+    a(f"v_bfe_u32 {vr(v + 3)}, {vr(v + 1)}, 2, 1")                  # q & 1: the block's second row
+    a(f"v_lshlrev_b32 {vr(v + 3)}, 5, {vr(v + 3)}")
+    a(f"v_bfe_u32 {vr(V_E)}, {vr(v + 1)}, 1, 1")                    # p >> 1: chunk pair
+    a(f"v_lshl_add_u32 {vr(v + 3)}, {vr(V_E)}, 6, {vr(v + 3)}")
+    a(f"v_and_b32 {vr(V_E)}, 1, {vr(v + 1)}")                       # p & 1: chunk of the pair
+    a(f"v_lshl_add_u32 {vr(v + 3)}, {vr(V_E)}, 4, {vr(v + 3)}")
+    a(f"v_lshrrev_b32 {vr(V_E)}, 1, {vr(v)}")                       # wn
+    a(f"v_lshl_add_u32 {vr(v + 3)}, {vr(V_E)}, 9, {vr(v + 3)}")     # 128 columns = 16 chunks
+    a(f"v_add_u32 {vr(v + 3)}, {HALF}, {vr(v + 3)}")
+    # the chunk's half: 8 par(p) for even fragments, 8 (1 - par(p)) for odd ones
+    a(f"v_bfe_u32 {vr(V_E)}, {vr(v + 1)}, 1, 1")
+    a(f"v_and_b32 {vr(V_E + 1)}, 1, {vr(v + 1)}")
+    a(f"v_xor_b32 {vr(V_E)}, {vr(V_E)}, {vr(V_E + 1)}")             # par(p)
+    a(f"v_lshlrev_b32 {vr(V_E)}, 3, {vr(V_E)}")
+    a(f"v_add_u32 {vr(V_E + 10)}, {vr(v + 3)}, {vr(V_E)}")
+    a(f"v_sub_u32 {vr(V_E + 11)}, {vr(v + 3)}, {vr(V_E)}")
+    a(f"v_add_u32 {vr(V_E + 11)}, 8, {vr(V_E + 11)}")
+    for dst, dblock, part in ((V_RW, 0, V_E + 10), (V_RWH, 2, V_E + 10), (V_RWO, 0, V_E + 11),
+                              (V_RWHO, 2, V_E + 11)):
+        a(f"v_add_u32 {vr(V_E + 1)}, {dblock}, {vr(v + 2)}")
+        wg.blockbase_v(a, V_E + 2, V_E + 1, V_E + 3)
+        a(f"v_add_u32 {vr(dst)}, {vr(V_E + 2)}, {vr(part)}")
+    for base, tg in NN_BASES:
+        a(f"v_add_u32 {vr(tg)}, {stage}, {vr(base)}")
+        a(f"v_xor_b32 {vr(tg)}, {vr(tg)}, {vr(base)}")
+
+
+def nn_m0_step(half: str, j: int) -> int:
+    """M0 from piece j to piece j + 1."""
+    wg = _wgrad()
+    return 4 * LINE if half == "x" else wg.blockbase(j + 1) - wg.blockbase(j)
+
+
+def nn_advance(half: str) -> list[str]:
+    if half == "x":
+        return advance("x")
+    return [f"s_add_u32 {sr(SRD_W)}, {sr(SRD_W)}, {sr(S_ADVW)}", f"s_addc_u32 {sr(SRD_W + 1)}, {sr(SRD_W + 1)}, 0"]
+
+
+def nn_frag_reads(i: int, sub: int) -> list[str]:
+    dst = (V_FW0 if sub == 0 else V_FW1) + 4 * i
+    off = nn_frag_offset(i, sub)
+    lo, hi = (V_RWO, V_RWHO) if i & 1 else (V_RW, V_RWH)
+    return [f"ds_read_b64_tr_b16 {vr(dst, 2)}, {vr(lo)} offset:{off}",
+            f"ds_read_b64_tr_b16 {vr(dst + 2, 2)}, {vr(hi)} offset:{off}"]
+
+
+def nn_prologue_dma(a: Asm):
+    """k-tiles 0 and 1 -> stages 0 and 1 (M0 bases end at stage 0)."""
+    for _ in range(2):
+        for half, srd_, vo, so, m0 in (("x", SRD_X, V_DX, S_SOX, S_M0X), ("w", SRD_W, V_DW, S_SOW, S_M0W)):
+            a(f"s_mov_b32 m0, {sr(m0)}")
+            for j in range(8):
+                a("s_nop 0")                     # M0 -> LDS-DMA hazard (dma())
+                soff = "0" if j == 0 else sr(so + j - 1)
+                a(f"buffer_load_dwordx4 {vr(vo)}, {sr(srd_, 4)}, {soff} offen lds")
+                if j < 7:
+                    a(f"s_add_u32 m0, m0, {nn_m0_step(half, j)}")
+            for ins in nn_advance(half):
+                a(ins)
+        a(f"s_xor_b32 {sr(S_M0X)}, {sr(S_M0X)}, {sr(S_M0XT)}")
+        a(f"s_xor_b32 {sr(S_M0W)}, {sr(S_M0W)}, {sr(S_M0WT)}")
+
+
+def iteration_nn(a: Asm, with_dma: bool, next_reads: bool):
+    """One 64-k tile of the NN loop on slot map NN_MAP (the keys of
+    iteration_map): a W slot carries the fragment's two transposed reads, so
+    a sub-step issues 8 + 16 reads; the 16 DMA pieces, both barriers and the
+    counted next-tile wait sit where the TN loop has them."""
+    m = SLOT_MAPS[NN_MAP]
+    split, lag = m.get("split", 0), m.get("m0_lag", 0)
+    slots: dict[int, list[str]] = {n: [] for n in range(128)}
+    for j, n in enumerate(m["x1"]):
+        slots[n].append(frag_read("x", j, 1))
+    for i, n in enumerate(m["w1"]):
+        slots[n] += nn_frag_reads(i, 1)
+    assert max(m["x1"]) < m["xbar"] and max(m["w1"]) < m["wbar"]
+    vm = 0
+    if with_dma:
+        for bar in (m["xbar"], m["wbar"]):
+            slots[bar].append("s_waitcnt lgkmcnt(0)")
+            slots[bar + split].append("s_barrier")
+        for half, key, bar in (("x", "xdma", m["xbar"]), ("w", "wdma", m["wbar"])):
+            srd_, vo, so, m0 = (SRD_X, V_DX, S_SOX, S_M0X) if half == "x" else (SRD_W, V_DW, S_SOW, S_M0W)
+            pos = m[key]
+            assert sorted(pos) == pos and pos[0] > bar + split and len(set(pos)) == 8
+            slots[pos[0] - 1].append(f"s_mov_b32 m0, {sr(m0)}")
+            for j, n in enumerate(pos):
+                soff = "0" if j == 0 else sr(so + j - 1)
+                slots[n].append(f"buffer_load_dwordx4 {vr(vo)}, {sr(srd_, 4)}, {soff} offen lds")
+                if j < 7:
+                    assert lag >= 1 and pos[j + 1] > n + lag      # an MFMA between an M0 write and the next piece
+                    slots[n + lag].append(f"s_add_u32 m0, m0, {nn_m0_step(half, j)}")
+            adv = m.get("adv", {}).get(half, pos[-1])
+            assert pos[-1] <= adv < 128
+            slots[adv] += nn_advance(half) + [f"s_xor_b32 {sr(m0)}, {sr(m0)}, {sr(m0 + 1)}"]
+        assert max(m["xdma"]) + lag < min(m["wdma"]) - 1          # one running M0
+        vm = sum(1 for n in m["xdma"] + m["wdma"] if n < m["wait"])
+    if next_reads:
+        w = m["wait"]
+        slots[w].append(f"s_waitcnt vmcnt({vm})")
+        slots[w + split] += ["s_barrier"] + [f"v_xor_b32 {vr(b)}, {vr(b)}, {vr(t)}"
+                                             for b, t in ((V_RX, V_RXT),) + NN_BASES]
+        assert min(m["x0"] + m["w0"]) > w + split and max(m["x0"] + m["w0"]) < 126
+        for j, n in enumerate(m["x0"]):
+            slots[n].append(frag_read("x", j, 0))
+        for i, n in enumerate(m["w0"]):
+            slots[n] += nn_frag_reads(i, 0)
+        slots[126].append("s_waitcnt lgkmcnt(0)")
+    for n in range(128):
+        sub, mm = divmod(n, 64)
+        i, j = divmod(mm, 8)
+        if n == 64:
+            a("s_waitcnt lgkmcnt(0)")
+        a(".p2alignl 3, 0xbf800000")
+        a(mfma(i, j, sub))
+        for ins in slots[n]:
+            a(ins)
+
+
+def kernel_nn(epi: str) -> tuple[str, str]:
+    """toa_gemm_nn_asm_<epi>: the kernarg block is KARG with `ldw` the row
+    stride of W [K, N] and ktiles = K / 64; tiles, tile order, M tail
+    (kernarg `m`) and argument guard are the TN kernels'."""
+    assert epi in NN_EPIS
+    name = f"toa_gemm_nn_asm_{epi}"
+    stage, lds = nn_layout()
+    g = globals()
+    saved = {k: g[k] for k in ("STAGE", "LDS_BYTES", "NN_SWAP")}
+    g["STAGE"], g["LDS_BYTES"] = stage, lds      # the X half's toggles, the delta epilogue's scratch
+    g["NN_SWAP"] = True                          # read_pair: lane groups 1, 2 hold their fragment pairs swapped
+    try:
+        a = Asm(prefix=f"nn_{epi}_")
+        a.raw(f".globl {name}")
+        a.raw(".p2align 8")
+        a.raw(f".type {name},@function")
+        a.raw(f"{name}:")
+        prologue(a, epi, form="nn")
+        nn_prologue_dma(a)
+        zero_acc(a)                                    # under the first tiles' flight
+        a("s_waitcnt vmcnt(16)")                       # own tile-0 pieces
+        a("s_barrier")                                 # everyone's
+        for j in range(8):
+            a(frag_read("x", j, 0))
+        for i in range(8):
+            for ins in nn_frag_reads(i, 0):
+                a(ins)
+        a("s_waitcnt lgkmcnt(0)")
+        a(f"s_sub_u32 {sr(S_LOOP)}, {sr(S_KT)}, 2")
+        l_loop, l_tail = a.fresh("loop"), a.fresh("tail")
+        a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
+        a(f"s_cbranch_scc1 {l_tail}")
+        a(".p2alignl 6, 0xbf800000")
+        a.label(l_loop)
+        iteration_nn(a, with_dma=True, next_reads=True)
+        a(f"s_sub_u32 {sr(S_LOOP)}, {sr(S_LOOP)}, 1")
+        a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
+        a(f"s_cbranch_scc0 {l_loop}")
+        a.label(l_tail)
+        iteration_nn(a, with_dma=False, next_reads=True)
+        iteration_nn(a, with_dma=False, next_reads=False)
+        a("s_nop 15")                                  # MFMA results -> VALU reads
+        a("s_nop 15")
+        for r, word in ((S_EX_SAME, 0x0000FFFF), (S_EX_SAME + 1, 0xFFFF0000), (S_EX_SWAP, 0xFFFF0000),
+                        (S_EX_SWAP + 1, 0x0000FFFF)):
+            a(f"s_mov_b32 {sr(r)}, {word:#x}")
+        epi_offsets(a, epi)
+        {"plain": epilogue_plain, "swiglu_bwd": epilogue_swiglu_bwd, "delta": epilogue_delta}[epi](a)
+        a.label(a.abort)
+        a("s_endpgm")
+        a.raw(f".size {name}, .-{name}")
+        desc, meta = _descriptor(name, lds_bytes=lds + (1024 if epi == "delta" else 0))
+        return "\n".join(a.out) + "\n" + desc, meta
+    finally:
+        g.update(saved)
+
+
 TRACE_REC = 32   # bytes per (workgroup, wave) trace record
 
 
@@ -2033,7 +2314,8 @@ def generate() -> str:
     for body, meta in (wgrad_gen.kernel(), wgrad_round4(), *attn_gen.all_kernels(), probe_kernel(), kernel("plain", trace=True),
                        _with_knobs({"timing": 1}, lambda: kernel("plain", variant="timing")),
                        _with_knobs({"timing": 2}, lambda: kernel("plain", variant="timing2")),
-                       *attn_bwd_gen.all_kernels()):
+                       *attn_bwd_gen.all_kernels(),
+                       *(kernel_nn(epi) for epi in NN_EPIS)):   # the data gradients on W as stored
         parts.append(body)
         metas.append(meta)
     # what hipcc emits after the last kernel: s_nop padding, so the

@@ -32,6 +32,15 @@ def pack(X, W, C, S, ldx_b, ldw_b, ldc_b, lds_b, K, tiles_m, tiles_n, fw_b=0, fc
     return bytes(buf)
 
 
+def pack_nn(X, W, C, S, ldx_b, ldw_b, ldc_b, lds_b, K, tiles_m, tiles_n, fw_b=0, fc_b=0,
+            tile_map=MAP_DEFAULT, M=None) -> bytes:
+    """The NN kernels' block (gemm_gen.kernel_nn): KARG as it is, W the weight
+    as stored ([K, N]: ldw_b its row stride, K its rows = the reduction,
+    tiles_n = N / 256 its column tiles), ktiles = K / 64."""
+    return pack(X, W, C, S, ldx_b, ldw_b, ldc_b, lds_b, K, tiles_m, tiles_n, fw_b=fw_b, fc_b=fc_b,
+                tile_map=tile_map, M=M)
+
+
 def tile_order(tiles_m: int, tiles_n: int, tile_map: int = MAP_DEFAULT) -> list[tuple[int, int]]:
     """(tm, tn) of workgroups 0, 1, ... as the prologue computes them: the
     XCD remap (workgroups b, b + 8, ... share an XCD; each XCD gets a

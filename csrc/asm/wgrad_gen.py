@@ -269,12 +269,7 @@ def prologue(a: Asm):
     v = V_T
     a(f"v_lshrrev_b32 {vr(v)}, 6, {vr(V_TID)}")                 # w
     a(f"v_and_b32 {vr(v + 1)}, 63, {vr(V_TID)}")                # lane
-    a(f"v_bfe_u32 {vr(v + 2)}, {vr(v + 1)}, 1, 1")              # s
-    a(f"v_lshl_add_u32 {vr(v + 2)}, {vr(v)}, 4, {vr(v + 2)}")   # row = 16 w + s
-    a(f"v_lshrrev_b32 {vr(v + 3)}, 2, {vr(v + 1)}")
-    a(f"v_and_b32 {vr(V_E)}, 1, {vr(v + 1)}")
-    a(f"v_lshl_add_u32 {vr(v + 3)}, {vr(v + 3)}, 1, {vr(V_E)}")  # chunk
-    a(f"v_lshlrev_b32 {vr(v + 3)}, 4, {vr(v + 3)}")             # chunk bytes
+    dma_lane(a, v, V_E)
     a(f"v_mul_lo_u32 {vr(V_DA)}, {vr(v + 2)}, {sr(S_LDA)}")
     a(f"v_add_u32 {vr(V_DA)}, {vr(V_DA)}, {vr(v + 3)}")
     a(f"v_mul_lo_u32 {vr(V_DB)}, {vr(v + 2)}, {sr(S_LDB)}")
@@ -327,6 +322,18 @@ def prologue(a: Asm):
 def zero_acc(a: Asm):
     for i in range(256):
         a(f"v_accvgpr_write_b32 {ar(i)}, 0")
+
+
+def dma_lane(a: Asm, v: int, t: int):
+    """A DMA piece's lane: v + 2 = its row 16 w + s of the wave's first block,
+    v + 3 = its chunk's byte offset (v = w, v + 1 = lane; t: scratch).  Shared
+    with the NN data-gradient kernels' W operand (gemm_gen.nn_lanes)."""
+    a(f"v_bfe_u32 {vr(v + 2)}, {vr(v + 1)}, 1, 1")              # s
+    a(f"v_lshl_add_u32 {vr(v + 2)}, {vr(v)}, 4, {vr(v + 2)}")   # row = 16 w + s
+    a(f"v_lshrrev_b32 {vr(v + 3)}, 2, {vr(v + 1)}")
+    a(f"v_and_b32 {vr(t)}, 1, {vr(v + 1)}")
+    a(f"v_lshl_add_u32 {vr(v + 3)}, {vr(v + 3)}, 1, {vr(t)}")   # chunk
+    a(f"v_lshlrev_b32 {vr(v + 3)}, 4, {vr(v + 3)}")             # chunk bytes
 
 
 def blockbase_v(a: Asm, dst: int, b: int, t: int):

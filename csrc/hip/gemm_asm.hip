@@ -79,11 +79,19 @@ const char* kNames[K_N] = {"toa_gemm_tn_asm_plain",    "toa_gemm_tn_asm_swiglu_f
                            // C = X W^T + R (epilogue_resadd: the output projection's residual add)
                            "toa_gemm_tn_asm_resadd"};
 
+// The NN-form kernels (gemm_gen.py kernel_nn: C = X W on W [K, N] as stored,
+// the data gradients without a transposed weight copy), a table of their own.
+enum { NN_PLAIN = 0, NN_SWIGLU_BWD = 1, NN_DELTA = 2, NN_N = 3 };
+const char* kNnNames[NN_N] = {"toa_gemm_nn_asm_plain", "toa_gemm_nn_asm_swiglu_bwd", "toa_gemm_nn_asm_delta"};
+
+constexpr int kNnBase = 1 << 16;  // get_fn / launch ids of the NN kernels: kNnBase + NN_*
+
 struct DevModule {
   std::once_flag once;
   hipError_t err = hipSuccess;
   hipModule_t mod = nullptr;
   hipFunction_t fn[K_N] = {};
+  hipFunction_t nn[NN_N] = {};
 };
 DevModule g_mod[kMaxDev];
 
@@ -98,9 +106,10 @@ hipFunction_t get_fn(int which, hipError_t* err) {
   std::call_once(m.once, [&m]() {
     m.err = hipModuleLoadData(&m.mod, toa_asm_blob);
     for (int i = 0; m.err == hipSuccess && i < K_N; ++i) m.err = hipModuleGetFunction(&m.fn[i], m.mod, kNames[i]);
+    for (int i = 0; m.err == hipSuccess && i < NN_N; ++i) m.err = hipModuleGetFunction(&m.nn[i], m.mod, kNnNames[i]);
   });
   *err = m.err;
-  return m.err == hipSuccess ? m.fn[which] : nullptr;
+  return m.err == hipSuccess ? (which >= kNnBase ? m.nn[which - kNnBase] : m.fn[which]) : nullptr;
 }
 
 struct __attribute__((packed)) Args {
@@ -155,7 +164,8 @@ int launch(int which, const Args& a, hipStream_t stream, unsigned grid = 0) {
   hipFunction_t fn = get_fn(which, &err);
   if (!fn) return (int)err;
   Args k = a;
-  if (which != K_DELTA) k.phase = phase_word(which);   // (the delta kernel's bytes 88..95 are a pointer)
+  if (which != K_DELTA && which != kNnBase + NN_DELTA)   // (the delta kernels' bytes 88..95 are a pointer)
+    k.phase = phase_word(which);
   size_t sz = sizeof(k);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   const unsigned nwg = grid ? grid : a.tiles_m * a.tiles_n;
@@ -715,6 +725,54 @@ extern "C" int toa_gemm_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t* W,
   a.fc = (uint32_t)H;
   memcpy(&a.phase, &ndelta, sizeof(ndelta));   // bytes 88..95
   return launch(K_DELTA, a, stream);
+}
+
+// ---- NN form: C[M][N] = X[M][K] W[K][N], W as stored (row stride ldw >= N).
+// N (the columns of W and C) a multiple of 256, K (the reduction, W's rows) a
+// multiple of 64 and >= 128, any 0 < M < 2^28 (kernarg `m`), strides multiples
+// of 8 elements, 16-byte aligned bases: the TN entries' checks with ldw
+// measured against N.  The tile order is the TN kernels' rule (the output is
+// [tokens, in features], like the forward).
+static bool nn_ok(int M, int N, int K, int64_t ldx, int64_t ldw, const void* X, const void* W, bool m_tail) {
+  return M > 0 && (m_tail || M % 256 == 0) && (int64_t)M < (1 << 28) && N > 0 && N % 256 == 0 && K >= 128 &&
+         K % 64 == 0 && ld_ok(ldx, K) && ld_ok(ldw, N) && al16(X) && al16(W);
+}
+
+extern "C" int toa_gemm_nn_asm(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc,
+                               int M, int N, int K, hipStream_t stream) {
+  if (!nn_ok(M, N, K, ldx, ldw, X, W, true) || !ld_ok(ldc, N) || !al16(C)) return (int)hipErrorInvalidValue;
+  Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
+  return launch(kNnBase + NN_PLAIN, a, stream);
+}
+
+// toa_gemm_asm_swiglu_bwd on Wd [K = D, F] as stored: dgu = SwiGLU'(gu) applied to ds = dY Wd.
+extern "C" int toa_gemm_nn_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16_t* Wd, int64_t ldw,
+                                          const bf16_t* GU, int64_t ldgu, bf16_t* dGU, int64_t lddgu, int M, int F,
+                                          int K, hipStream_t stream) {
+  if (!nn_ok(M, F, K, ldy, ldw, dY, Wd, true) || !ld_ok(ldgu, 2 * F) || !ld_ok(lddgu, 2 * F) || !al16(GU) ||
+      !al16(dGU))
+    return (int)hipErrorInvalidValue;
+  Args a = base_args(dY, ldy, Wd, ldw, dGU, lddgu, M, F / 256, K);
+  a.S = (uint64_t)GU;
+  a.lds = (uint32_t)(ldgu * 2);
+  a.fc = (uint32_t)(F * 2);
+  return launch(kNnBase + NN_SWIGLU_BWD, a, stream);
+}
+
+// toa_gemm_asm_delta on Wo [K, N] as stored: dX = dY Wo with the attention
+// backward's delta fused (whole tiles only: M % S == 0, S % 256 == 0).
+extern "C" int toa_gemm_nn_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
+                                     int64_t ldc, const bf16_t* O, float* ndelta, int M, int N, int K, int S, int H,
+                                     hipStream_t stream) {
+  if (!nn_ok(M, N, K, ldx, ldw, X, W, false) || !ld_ok(ldc, N) || !al16(C) || !al16(O) || ndelta == nullptr ||
+      ((uintptr_t)ndelta & 3) || H <= 0 || (int64_t)H * 128 != N || S <= 0 || S % 256 || M % S)
+    return (int)hipErrorInvalidValue;
+  Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
+  a.S = (uint64_t)O;
+  a.fw = (uint32_t)S;
+  a.fc = (uint32_t)H;
+  memcpy(&a.phase, &ndelta, sizeof(ndelta));   // bytes 88..95
+  return launch(kNnBase + NN_DELTA, a, stream);
 }
 
 // C = X W^T + R, R bf16 laid out like C (gemm_gen.py epilogue_resadd).

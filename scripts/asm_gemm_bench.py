@@ -338,6 +338,51 @@ def wgrad(a):
     print(json.dumps({"wgrad": res}))
 
 
+def nn_forms(a):
+    """The five data-gradient forms dX [T, in] = dY [T, out] W [out, in]: the
+    NN kernel on W as stored (toa_gemm_nn_asm) against the TN kernel on its
+    transposed copy (toa_gemm_asm), alternating in one process, every round in
+    the order nn, tn, tn, nn; results checked against each other first."""
+    T = a.tokens
+    torch.manual_seed(0)
+    res = {}
+    for name, (K_in, N_out) in FORMS.items():          # forward: x [T, K_in] W [N_out, K_in]
+        if a.forms and name not in a.forms.split(","):
+            continue
+        dy = torch.randn(T, N_out, device="cuda").to(torch.bfloat16)
+        w = (torch.randn(N_out, K_in, device="cuda") / N_out ** 0.5).to(torch.bfloat16)
+        wt = w.t().contiguous()
+        dx_nn = torch.empty(T, K_in, device="cuda", dtype=torch.bfloat16)
+        dx_tn = torch.empty_like(dx_nn)
+
+        def run_nn():
+            _lib.call("toa_gemm_nn_asm", _lib.ptr(dy), N_out, _lib.ptr(w), K_in, _lib.ptr(dx_nn), K_in, T, K_in,
+                      N_out, _lib.stream(dy))
+
+        def run_tn():
+            asm(dy, wt, dx_tn)
+
+        run_nn()
+        run_tn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(dx_nn, dx_tn))
+        ts = {"nn": [], "tn": []}
+        for _ in range(a.rounds):
+            for arm in ("nn", "tn", "tn", "nn"):
+                ts[arm].append(timer(run_nn if arm == "nn" else run_tn, a.reps))
+        flops = 2.0 * T * K_in * N_out
+        rec = {"shape": [T, K_in, N_out], "bit_identical": same, "rel": rel(dx_nn, dx_tn)}
+        for arm, v in ts.items():
+            med = statistics.median(v)
+            rec[arm] = {"ms": round(med, 4), "min": round(min(v), 4), "max": round(max(v), 4),
+                        "pflops": round(flops / med / 1e12, 3)}
+        rec["nn_over_tn"] = round(rec["nn"]["ms"] / rec["tn"]["ms"], 4)
+        res[name] = rec
+        print(json.dumps({name: rec}), flush=True)
+        del dy, w, wt, dx_nn, dx_tn
+    print(json.dumps({"nn_dgrad": res, "tokens": T}))
+
+
 def timer(fn, reps):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     fn()
@@ -483,7 +528,11 @@ def main():
                                                      "log2 group | 16 for column groups; the per-shape default "
                                                      "is gemm_asm.hip wgrad_tile_map)")
     ap.add_argument("--wgrad-splits", default="", help="extra asm arms with every tile cut into S K-pieces, e.g. 1,2,3")
+    ap.add_argument("--nn", action="store_true", help="data-gradient forms: the NN kernel on W vs the TN kernel on W^T")
     a = ap.parse_args()
+    if a.nn:
+        nn_forms(a)
+        return
     if a.probe:
         probe()
         return

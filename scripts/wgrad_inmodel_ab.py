@@ -20,6 +20,9 @@ qkvrope=0|1 (the QKV projection's GEMM applies RoPE and the head-major relayout,
 dfused=0|1 (the attention delta rows from the output projection's GEMM, or the attention's own pass),
 resadd=0|1 (the residual add in the output projection's epilogue, or in the RMSNorm),
 adamcap=N (the flat AdamW grid cap / 1024, toa_set_stream_variant),
+dgrad=wt|nn (the data gradients on the W^T copies, or on W as stored through the NN-form kernels: the weights'
+``_toa_wt`` views are hidden for the window; the copies stay built and refreshed in both arms, so the arms differ by
+the GEMM form alone, not by the refresh pass or the memory the copies take),
 or the presets r4 (every round-4 default kernel: nosk GEMMs, the round-4
 weight-gradient schedule, the HIP attention forward and dK/dV) and head
 (this tree's defaults).  Same-process windows remove the box-to-box spread
@@ -105,6 +108,13 @@ def apply(arm: str):
         elif key == "resadd":   # the residual add in the output projection's epilogue (1) or in the RMSNorm (0)
             import os
             os.environ["TOA_RESADD_FUSED"] = val
+        elif key == "dgrad":
+            gemm.set_dgrad_form(val)
+            for _, _, p, view in TR.wt.items:
+                if val == "nn":
+                    p.__dict__.pop("_toa_wt", None)
+                else:
+                    p._toa_wt = view
         elif key == "wmap":   # weight-gradient tile order: -1 = the per-shape rule, else a map word
             _lib.call("toa_wgrad_asm_set_map", int(val))
         elif key == "adamcap":

@@ -335,14 +335,79 @@ def linear_resadd(x2: torch.Tensor, w: torch.Tensor, r2: torch.Tensor) -> torch.
     return y
 
 
+# Data gradient dX = dY W of a weight without a transposed copy: "wt" (default)
+# leaves it to the library, as before; "nn" runs the NN-form assembly kernel on
+# W as stored (csrc/asm/gemm_gen.py kernel_nn), so no copy is needed at all --
+# ops.wt.enabled_default then builds none.  An explicit ``_toa_wt`` always wins.
+_DGRAD_FORM = None
+
+
+def dgrad_form() -> str:
+    """``wt`` (default) or ``nn``; ``TOA_DGRAD`` sets it without a code change."""
+    global _DGRAD_FORM
+    if _DGRAD_FORM is None:
+        forced = os.environ.get("TOA_DGRAD", "")
+        if forced not in ("", "wt", "nn"):
+            raise ValueError(f"TOA_DGRAD={forced!r}: expected wt or nn")
+        _DGRAD_FORM = forced or "wt"
+    return _DGRAD_FORM
+
+
+def set_dgrad_form(name: str):
+    global _DGRAD_FORM
+    if name not in ("wt", "nn"):
+        raise ValueError(f"unknown data-gradient form {name!r}")
+    _DGRAD_FORM = name
+
+
+def _why_not_nn(dy2: torch.Tensor, w: torch.Tensor) -> str:
+    """The first check of toa_gemm_nn_asm that (dy2 [M, K], w [K, N]) fails, "" if none."""
+    if not _lib.has("toa_gemm_nn_asm"):
+        return "library built without toa_gemm_nn_asm"
+    if not (dy2.is_cuda and dy2.dim() == 2 and w.dim() == 2):
+        return "not 2-D GPU tensors"
+    if dy2.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        return f"dtype {dy2.dtype}/{w.dtype}, not bf16"
+    M, K = dy2.shape
+    N = w.shape[1]
+    if w.shape[0] != K:
+        return f"dY has {K} columns, W {w.shape[0]} rows"
+    if not 0 < M < 1 << 28:
+        return f"M={M} (tokens) outside 1 .. 2^28 - 1"
+    if N <= 0 or N % 256:
+        return f"N={N} (in features) not a multiple of 256"
+    if K % 64 or K < 128:
+        return f"K={K} (out features) not a multiple of 64 >= 128"
+    for t, cols in ((dy2, K), (w, N)):
+        if t.stride(1) != 1 or t.stride(0) < cols or t.stride(0) % 8 or t.stride(0) >= 1 << 23 or t.data_ptr() % 16:
+            return "layout: non-unit column stride, unaligned rows or base"
+    return ""
+
+
+def nn_takes(dy2: torch.Tensor, w: torch.Tensor) -> bool:
+    """Operands the NN-form assembly GEMM takes for dX = dy2 w: the host-side
+    checks of csrc/hip/gemm_asm.hip's toa_gemm_nn_asm (``nn_ok`` / ``ld_ok`` /
+    ``al16``) on dy2 [M, K] and w [K, N] as stored, under the ``asm`` policy:
+    any 0 < M < 2^28, N a multiple of 256, K a multiple of 64 and >= 128."""
+    return _MODE == "asm" and not _why_not_nn(dy2, w) and _lib.use_hip(dy2)
+
+
 def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     wt = getattr(w, "_toa_wt", None)
     if wt is not None:  # W^T kept by ops.wt.TransposedWeights: dx = dy (W^T)^T, the forward's form
         return linear_fwd(dy2, wt)
+    why = "no transposed weight copy (ops/wt.py) for this weight"
+    if _MODE == "asm" and dgrad_form() == "nn":
+        if nn_takes(dy2, w):
+            M, N = dy2.shape[0], w.shape[1]
+            dx = torch.empty(M, N, device=dy2.device, dtype=dy2.dtype)
+            _lib.call("toa_gemm_nn_asm", _lib.ptr(dy2), dy2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(dx), N,
+                      M, N, dy2.shape[1], _lib.stream(dy2))
+            return dx
+        why = f"NN form refused: {_why_not_nn(dy2, w) or 'not on the HIP device'}"
     lib_ok = _ok(dy2, w)
     if _MODE == "asm" and dy2.is_cuda and dy2.dim() == 2 and w.dim() == 2:
-        _fallback("dgrad", (dy2.shape[0], w.shape[1], dy2.shape[1]), "hipBLASLt" if lib_ok else "torch.matmul",
-                  "no transposed weight copy (ops/wt.py) for this weight")
+        _fallback("dgrad", (dy2.shape[0], w.shape[1], dy2.shape[1]), "hipBLASLt" if lib_ok else "torch.matmul", why)
     if not lib_ok:
         return torch.matmul(dy2, w)
     M, N = dy2.shape
@@ -367,9 +432,19 @@ def swiglu_gate_up(x2: torch.Tensor, wgu: torch.Tensor):
 
 def swiglu_down_dgrad(d2: torch.Tensor, wd: torch.Tensor, gu: torch.Tensor):
     """dgu = SwiGLU-backward(gu, ds = d2 Wd) from ONE assembly GEMM on the
-    transposed weight copy (ops/wt.py) with the SwiGLU backward in its
-    epilogue (ds is never stored); None when the kernel cannot take it."""
+    transposed weight copy (ops/wt.py) -- or, without one under
+    ``dgrad_form() == "nn"``, on Wd as stored -- with the SwiGLU backward in
+    its epilogue (ds is never stored); None when the kernel cannot take it."""
     wdt = getattr(wd, "_toa_wt", None)
+    if wdt is None and dgrad_form() == "nn":     # on Wd [D, F] as stored (the NN form)
+        if not (nn_takes(d2, wd) and _lib.has("toa_gemm_nn_asm_swiglu_bwd") and gu.is_contiguous()
+                and gu.shape[1] == 2 * wd.shape[1] and gu.data_ptr() % 16 == 0):
+            return None
+        M, F = d2.shape[0], wd.shape[1]
+        dgu = torch.empty_like(gu)
+        _lib.call("toa_gemm_nn_asm_swiglu_bwd", _lib.ptr(d2), d2.stride(0), _lib.ptr(wd), wd.stride(0), _lib.ptr(gu),
+                  2 * F, _lib.ptr(dgu), 2 * F, M, F, d2.shape[1], _lib.stream(d2))
+        return dgu
     if wdt is None or not (asm_takes(d2, wdt) and gu.is_contiguous() and gu.shape[1] == 2 * wdt.shape[0]
                            and gu.data_ptr() % 16 == 0):
         return None

@@ -436,7 +436,8 @@ class _AttnOutProj(torch.autograd.Function):
     (toa_gemm_asm_delta) dots each stored dO row with O per head in its
     epilogue and puts them into the sub-block's link, so the attention
     backward (_rope_attn_dqkv) skips its pass over dO and O.  Elsewhere (no
-    link, no W^T copy, other shapes) the plain linear."""
+    link, neither a W^T copy nor the NN data-gradient form, other shapes) the
+    plain linear."""
 
     @staticmethod
     def forward(ctx, o2, wo, B, S, H, residual, link):
@@ -455,13 +456,15 @@ class _AttnOutProj(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         dx = None
         wt = getattr(wo, "_toa_wt", None)
-        if (ctx.needs_input_grad[0] and ctx.link is not None and wt is not None and dy2.stride(-1) == 1
-                and wt.stride(-1) == 1 and o2.is_contiguous() and attn_delta_fused_enabled()
-                and _lib.has("toa_gemm_asm_delta") and gemm.mode() == "asm"):
+        # the delta GEMM on the W^T copy, or without one under dgrad_form "nn" on wo as stored
+        fn, wmat = ("toa_gemm_asm_delta", wt) if wt is not None else ("toa_gemm_nn_asm_delta", wo)
+        if (ctx.needs_input_grad[0] and ctx.link is not None and (wt is not None or gemm.dgrad_form() == "nn")
+                and dy2.stride(-1) == 1 and wmat.stride(-1) == 1 and o2.is_contiguous()
+                and attn_delta_fused_enabled() and _lib.has(fn) and gemm.mode() == "asm"):
             T, N = o2.shape
             dx = torch.empty_like(o2)
             nd = torch.empty(B * H * S, device=o2.device, dtype=torch.float32)
-            rc = _lib.call_ret("toa_gemm_asm_delta", _lib.ptr(dy2), dy2.stride(0), _lib.ptr(wt), wt.stride(0),
+            rc = _lib.call_ret(fn, _lib.ptr(dy2), dy2.stride(0), _lib.ptr(wmat), wmat.stride(0),
                                _lib.ptr(dx), dx.stride(0), _lib.ptr(o2), _lib.ptr(nd), T, N, dy2.shape[1], S, H,
                                _lib.stream(dy2))
             if rc == 0:
@@ -469,7 +472,7 @@ class _AttnOutProj(torch.autograd.Function):
             elif rc == 1:   # hipErrorInvalidValue: a shape it does not take
                 dx = None
             else:
-                raise RuntimeError(f"toa_gemm_asm_delta failed with hipError {rc}")
+                raise RuntimeError(f"{fn} failed with hipError {rc}")
         if dx is None and ctx.needs_input_grad[0]:
             dx = gemm.linear_dgrad(dy2, wo)
         dw = accumulate_mm(wo, dy2.t(), o2)

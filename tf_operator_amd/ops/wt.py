@@ -14,6 +14,10 @@ HBM-bound ``toa_transpose_bf16`` kernel (csrc/hip/transpose.hip, ~7 ms per
 step at 8B).  ``param._toa_wt`` is the [in, out] view that
 :func:`tf_operator_amd.ops.gemm.linear_dgrad` picks up.
 
+The copies are one of two ways: under ``TOA_DGRAD=nn`` (ops.gemm.dgrad_form)
+the data gradient reads ``W`` itself through the NN-form assembly GEMM and no
+copy is built.
+
 Anything that rewrites the weights outside the optimizer (checkpoint load,
 rank-0 broadcast) must call :meth:`refresh`; :class:`FlatParams` does it
 through its ``on_param_change`` listeners.
@@ -42,7 +46,12 @@ def transpose_into(dst: torch.Tensor, src: torch.Tensor):
 
 
 def enabled_default(device) -> bool:
-    return torch.device(device).type == "cuda" and os.environ.get("TOA_DGRAD_WT", "1") != "0"
+    from . import gemm
+
+    # no copies under the NN data-gradient form -- which only the assembly policy runs: under a library
+    # policy the copies stay, since the library's NN form is the slow one they were built to avoid
+    nn = gemm.dgrad_form() == "nn" and gemm.mode() in ("asm", "auto")
+    return torch.device(device).type == "cuda" and os.environ.get("TOA_DGRAD_WT", "1") != "0" and not nn
 
 
 class TransposedWeights:

@@ -182,16 +182,70 @@ __device__ __forceinline__ void adam_elem(float g, float& p, float& m, float& v,
   p = p - lr * (m * inv_bc1) / denom - lrwd * p;
 }
 
-template <bool GRAD_BF16, bool NT>
+// ---------------------------------------------------------------------------
+// bf16 moments (FlatAdamW state_dtype=bf16): m and v are stored as bf16 and
+// rounded STOCHASTICALLY after the fp32 update, so a change below half a
+// bf16 step (v at beta2 = 0.999 moves 0.1 % per step) still moves the
+// expectation.  Integer arithmetic only: ops/optim.py mirrors it bit for bit
+// (sr_bf16_reference, sr_hash_reference).
+//   sr_bf16(x, r): bits (u + r) >> 16 for finite x (u = bits of x, r 16 bits);
+//                  u >> 16 for inf / NaN, a NaN kept a NaN.
+//   sr_hash(i, k): one 32-bit draw per element, a pure function of the
+//                  element's 64-bit index i in the FLAT buffer and
+//                  k = 0x9E3779B9 * step + seed; low 16 bits round m, high 16 v.
+// How the buffer is cut into launches therefore cannot change a bit.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t mix32(uint32_t h) {  // murmur3 finaliser
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+__device__ __forceinline__ uint32_t sr_key(int step, uint32_t seed) { return 0x9E3779B9u * (uint32_t)step + seed; }
+
+__device__ __forceinline__ uint32_t sr_hash(int64_t i, uint32_t key) {
+  return mix32((uint32_t)i ^ mix32((uint32_t)((uint64_t)i >> 32) + key));
+}
+
+__device__ __forceinline__ uint32_t sr_bf16(float x, uint32_t r) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7f800000u) != 0x7f800000u) return (u + r) >> 16;
+  return (u >> 16) | ((u & 0x007fffffu) ? 0x40u : 0u);
+}
+
+// Round and pack the 8 updated (m, v) pairs of the chunk whose first element
+// has flat index e0 (a multiple of 8: the whole chunk shares the upper half
+// of the index, so its inner mix32 is computed once).
+__device__ __forceinline__ void sr_pack8(const float* mm, const float* vv, int64_t e0, uint32_t key, u32x4& mo,
+                                         u32x4& vo) {
+  const uint32_t inner = mix32((uint32_t)((uint64_t)e0 >> 32) + key), lo = (uint32_t)e0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t h0 = mix32((lo + 2 * j) ^ inner), h1 = mix32((lo + 2 * j + 1) ^ inner);
+    mo[j] = sr_bf16(mm[2 * j], h0 & 0xffffu) | (sr_bf16(mm[2 * j + 1], h1 & 0xffffu) << 16);
+    vo[j] = sr_bf16(vv[2 * j], h0 >> 16) | (sr_bf16(vv[2 * j + 1], h1 >> 16) << 16);
+  }
+}
+
+// MT: the moments' storage type, float (16 B of the 28 B / parameter) or
+// bf16_t (8 of 20).  base / seed / step feed the rounding of bf16 moments
+// only; the fp32 instantiations ignore them.
+template <bool GRAD_BF16, bool NT, typename MT = float>
 __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ master, bf16_t* __restrict__ param,
-                                                         void* __restrict__ grad, int zero_grad, float* __restrict__ m,
-                                                         float* __restrict__ v, int64_t n8, float lr, float b1,
+                                                         void* __restrict__ grad, int zero_grad, MT* __restrict__ m,
+                                                         MT* __restrict__ v, int64_t n8, float lr, float b1,
                                                          float b2, float eps, float wd, float inv_bc1,
                                                          float inv_sqrt_bc2, float grad_scale,
                                                          const float* __restrict__ norm_sq, float max_norm,
-                                                         const int* __restrict__ step_dev) {
+                                                         const int* __restrict__ step_dev, int step, int64_t base,
+                                                         uint32_t seed) {
+  constexpr bool MB = sizeof(MT) == 2;   // bf16 moments
   const float scale = adam_prologue(b1, b2, grad_scale, norm_sq, max_norm, step_dev, inv_bc1, inv_sqrt_bc2);
   const float omb1 = 1.f - b1, omb2 = 1.f - b2, lrwd = lr * wd;
+  const uint32_t key = MB ? sr_key(step_dev != nullptr ? step_dev[0] : step, seed) : 0u;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8;
        i += (int64_t)gridDim.x * blockDim.x) {
     float g[8], p[8], mm[8], vv[8];
@@ -208,28 +262,52 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ mas
       }
     }
     f32x4* pm = (f32x4*)master + 2 * i;
-    f32x4* mv = (f32x4*)m + 2 * i;
-    f32x4* vvp = (f32x4*)v + 2 * i;
-    f32x4 p0 = ld_s(pm, NT), p1 = ld_s(pm + 1, NT), m0 = ld_s(mv, NT), m1 = ld_s(mv + 1, NT),
-          v0 = ld_s(vvp, NT), v1 = ld_s(vvp + 1, NT);
+    f32x4 p0 = ld_s(pm, NT), p1 = ld_s(pm + 1, NT);
+    if constexpr (MB) {
+      u32x4* mv = (u32x4*)m + i;
+      u32x4* vvp = (u32x4*)v + i;
+      const u32x4 mb = ld_s(mv, NT), vb = ld_s(vvp, NT);
+      unpack8(mb, mm);
+      unpack8(vb, vv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p[j] = p0[j]; p[j + 4] = p1[j];
-      mm[j] = m0[j]; mm[j + 4] = m1[j];
-      vv[j] = v0[j]; vv[j + 4] = v1[j];
+      for (int j = 0; j < 4; ++j) {
+        p[j] = p0[j]; p[j + 4] = p1[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        adam_elem(g[j], p[j], mm[j], vv[j], scale, b1, b2, omb1, omb2, lr, lrwd, eps, inv_bc1, inv_sqrt_bc2);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        p0[j] = p[j]; p1[j] = p[j + 4];
+      }
+      u32x4 mo, vo;
+      sr_pack8(mm, vv, base + 8 * i, key, mo, vo);
+      st_s(pm, p0, NT); st_s(pm + 1, p1, NT);
+      st_s(mv, mo, NT);
+      st_s(vvp, vo, NT);
+    } else {
+      f32x4* mv = (f32x4*)m + 2 * i;
+      f32x4* vvp = (f32x4*)v + 2 * i;
+      f32x4 m0 = ld_s(mv, NT), m1 = ld_s(mv + 1, NT), v0 = ld_s(vvp, NT), v1 = ld_s(vvp + 1, NT);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        p[j] = p0[j]; p[j + 4] = p1[j];
+        mm[j] = m0[j]; mm[j + 4] = m1[j];
+        vv[j] = v0[j]; vv[j + 4] = v1[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        adam_elem(g[j], p[j], mm[j], vv[j], scale, b1, b2, omb1, omb2, lr, lrwd, eps, inv_bc1, inv_sqrt_bc2);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        p0[j] = p[j]; p1[j] = p[j + 4];
+        m0[j] = mm[j]; m1[j] = mm[j + 4];
+        v0[j] = vv[j]; v1[j] = vv[j + 4];
+      }
+      st_s(pm, p0, NT); st_s(pm + 1, p1, NT);
+      st_s(mv, m0, NT); st_s(mv + 1, m1, NT);
+      st_s(vvp, v0, NT); st_s(vvp + 1, v1, NT);
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      adam_elem(g[j], p[j], mm[j], vv[j], scale, b1, b2, omb1, omb2, lr, lrwd, eps, inv_bc1, inv_sqrt_bc2);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p0[j] = p[j]; p1[j] = p[j + 4];
-      m0[j] = mm[j]; m1[j] = mm[j + 4];
-      v0[j] = vv[j]; v1[j] = vv[j + 4];
-    }
-    st_s(pm, p0, NT); st_s(pm + 1, p1, NT);
-    st_s(mv, m0, NT); st_s(mv + 1, m1, NT);
-    st_s(vvp, v0, NT); st_s(vvp + 1, v1, NT);
     if (param != nullptr) st_s((u32x4*)param + i, pack8(p), NT);
   }
 }
@@ -246,16 +324,22 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ mas
 // A workgroup walks 128 x 128 tiles; each pass of its 256 threads updates
 // 16 rows x 128 columns (16 lanes per 256-byte row).
 // ---------------------------------------------------------------------------
+// MT = bf16_t: bf16 moments, rounded by sr_pack8 with the flat index base +
+// (the element's offset in the weight) -- the bits of the flat kernel.
+template <typename MT = float>
 __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ master, bf16_t* __restrict__ param,
                                                        bf16_t* __restrict__ grad, int zero_grad,
-                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       MT* __restrict__ m, MT* __restrict__ v,
                                                        bf16_t* __restrict__ wt, int64_t ldt, int R, int C, float lr,
                                                        float b1, float b2, float eps, float wd, float inv_bc1,
                                                        float inv_sqrt_bc2, float grad_scale,
-                                                       const float* __restrict__ norm_sq, float max_norm) {
+                                                       const float* __restrict__ norm_sq, float max_norm, int step,
+                                                       int64_t base, uint32_t seed) {
+  constexpr bool MB = sizeof(MT) == 2;
   __shared__ u32x4 tile[128 * 16];
   const float scale = adam_prologue(b1, b2, grad_scale, norm_sq, max_norm, nullptr, inv_bc1, inv_sqrt_bc2);
   const float omb1 = 1.f - b1, omb2 = 1.f - b2, lrwd = lr * wd;
+  const uint32_t key = MB ? sr_key(step, seed) : 0u;
   const int tid = threadIdx.x;
   const int lr_ = tid >> 4, lc = tid & 15;   // update: row lr_ + 16 p, chunk lc
   const int a = tid & 15, bq = tid >> 4;     // transposed store: rows 8a.., chunk bq
@@ -267,7 +351,7 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
     __syncthreads();   // the previous tile's transposed reads are done
 #pragma unroll 1
     for (int pp = 0; pp < 8; pp += 2) {
-      u32x4 gb[2];
+      u32x4 gb[2], mb[2], vb[2];
       f32x4 pv[2][2], mv[2][2], vv[2][2];
       int64_t e8[2];
 #pragma unroll
@@ -277,10 +361,15 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
         gb[q] = ld_s((const u32x4*)grad + e8[q], true);
         pv[q][0] = ld_s((const f32x4*)master + 2 * e8[q], true);
         pv[q][1] = ld_s((const f32x4*)master + 2 * e8[q] + 1, true);
-        mv[q][0] = ld_s((const f32x4*)m + 2 * e8[q], true);
-        mv[q][1] = ld_s((const f32x4*)m + 2 * e8[q] + 1, true);
-        vv[q][0] = ld_s((const f32x4*)v + 2 * e8[q], true);
-        vv[q][1] = ld_s((const f32x4*)v + 2 * e8[q] + 1, true);
+        if constexpr (MB) {
+          mb[q] = ld_s((const u32x4*)m + e8[q], true);
+          vb[q] = ld_s((const u32x4*)v + e8[q], true);
+        } else {
+          mv[q][0] = ld_s((const f32x4*)m + 2 * e8[q], true);
+          mv[q][1] = ld_s((const f32x4*)m + 2 * e8[q] + 1, true);
+          vv[q][0] = ld_s((const f32x4*)v + 2 * e8[q], true);
+          vv[q][1] = ld_s((const f32x4*)v + 2 * e8[q] + 1, true);
+        }
       }
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
@@ -288,6 +377,15 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
         float g[8], p[8];
         unpack8(gb[q], g);
         if (zero_grad) st16(grad + e8[q] * 8, u32x4{0, 0, 0, 0});
+        if constexpr (MB) {
+          float t[8];
+          unpack8(mb[q], t);
+          mv[q][0] = f32x4{t[0], t[1], t[2], t[3]};
+          mv[q][1] = f32x4{t[4], t[5], t[6], t[7]};
+          unpack8(vb[q], t);
+          vv[q][0] = f32x4{t[0], t[1], t[2], t[3]};
+          vv[q][1] = f32x4{t[4], t[5], t[6], t[7]};
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -301,10 +399,21 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
           }
         st_s((f32x4*)master + 2 * e8[q], pv[q][0], true);
         st_s((f32x4*)master + 2 * e8[q] + 1, pv[q][1], true);
-        st_s((f32x4*)m + 2 * e8[q], mv[q][0], true);
-        st_s((f32x4*)m + 2 * e8[q] + 1, mv[q][1], true);
-        st_s((f32x4*)v + 2 * e8[q], vv[q][0], true);
-        st_s((f32x4*)v + 2 * e8[q] + 1, vv[q][1], true);
+        if constexpr (MB) {
+          const float mf[8] = {mv[q][0][0], mv[q][0][1], mv[q][0][2], mv[q][0][3],
+                               mv[q][1][0], mv[q][1][1], mv[q][1][2], mv[q][1][3]};
+          const float vf[8] = {vv[q][0][0], vv[q][0][1], vv[q][0][2], vv[q][0][3],
+                               vv[q][1][0], vv[q][1][1], vv[q][1][2], vv[q][1][3]};
+          u32x4 mo, vo;
+          sr_pack8(mf, vf, base + 8 * e8[q], key, mo, vo);
+          st_s((u32x4*)m + e8[q], mo, true);
+          st_s((u32x4*)v + e8[q], vo, true);
+        } else {
+          st_s((f32x4*)m + 2 * e8[q], mv[q][0], true);
+          st_s((f32x4*)m + 2 * e8[q] + 1, mv[q][1], true);
+          st_s((f32x4*)v + 2 * e8[q], vv[q][0], true);
+          st_s((f32x4*)v + 2 * e8[q] + 1, vv[q][1], true);
+        }
         const u32x4 pk = pack8(p);
         st_s((u32x4*)param + e8[q], pk, true);
         tile[r * 16 + (lc ^ ((r >> 3) & 15))] = pk;
@@ -321,21 +430,41 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
   }
 }
 
-extern "C" int toa_adamw_wt(float* master, bf16_t* param, bf16_t* grad, int zero_grad, float* m, float* v,
-                            bf16_t* wt, int64_t ldt, int R, int C, float lr, float beta1, float beta2, float eps,
-                            float weight_decay, int step, float grad_scale, const float* norm_sq, float max_norm,
-                            hipStream_t stream) {
+template <typename MT>
+static int adamw_wt_launch(float* master, bf16_t* param, bf16_t* grad, int zero_grad, MT* m, MT* v, bf16_t* wt,
+                           int64_t ldt, int R, int C, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, int step, float grad_scale, const float* norm_sq, float max_norm,
+                           int64_t base, uint32_t seed, hipStream_t stream) {
   if (R <= 0 || C <= 0 || R % 128 || C % 128 || ldt < R || ldt % 8 || ((uintptr_t)master & 15) ||
       ((uintptr_t)m & 15) || ((uintptr_t)v & 15) || ((uintptr_t)grad & 15) || ((uintptr_t)param & 15) ||
-      ((uintptr_t)wt & 15) || step < 1)
+      ((uintptr_t)wt & 15) || step < 1 || base < 0 || base % 8)
     return (int)hipErrorInvalidValue;
   const float inv_bc1 = 1.f / (1.f - powf(beta1, (float)step));
   const float inv_sqrt_bc2 = 1.f / sqrtf(1.f - powf(beta2, (float)step));
   const int64_t tiles = (int64_t)(R / 128) * (C / 128);
   const int grid = (int)(tiles < 16384 ? tiles : 16384);
-  hipLaunchKernelGGL(adamw_wt_kernel, dim3(grid), dim3(256), 0, stream, master, param, grad, zero_grad, m, v, wt, ldt,
-                     R, C, lr, beta1, beta2, eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale, norm_sq, max_norm);
+  hipLaunchKernelGGL(adamw_wt_kernel<MT>, dim3(grid), dim3(256), 0, stream, master, param, grad, zero_grad, m, v, wt,
+                     ldt, R, C, lr, beta1, beta2, eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale, norm_sq,
+                     max_norm, step, base, seed);
   return (int)hipGetLastError();
+}
+
+extern "C" int toa_adamw_wt(float* master, bf16_t* param, bf16_t* grad, int zero_grad, float* m, float* v,
+                            bf16_t* wt, int64_t ldt, int R, int C, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, float grad_scale, const float* norm_sq, float max_norm,
+                            hipStream_t stream) {
+  return adamw_wt_launch(master, param, grad, zero_grad, m, v, wt, ldt, R, C, lr, beta1, beta2, eps, weight_decay,
+                         step, grad_scale, norm_sq, max_norm, 0, 0u, stream);
+}
+
+// bf16 moments, stochastically rounded: `base` is the flat index of the
+// weight's first element (a multiple of 8), `seed` the optimizer's.
+extern "C" int toa_adamw_wt_bf16s(float* master, bf16_t* param, bf16_t* grad, int zero_grad, bf16_t* m, bf16_t* v,
+                                  bf16_t* wt, int64_t ldt, int R, int C, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int step, float grad_scale, const float* norm_sq,
+                                  float max_norm, int64_t base, uint32_t seed, hipStream_t stream) {
+  return adamw_wt_launch(master, param, grad, zero_grad, m, v, wt, ldt, R, C, lr, beta1, beta2, eps, weight_decay,
+                         step, grad_scale, norm_sq, max_norm, base, seed, stream);
 }
 
 // Variant switch for in-process A/B (scripts/stream_ab.py,
@@ -357,9 +486,11 @@ extern "C" int toa_set_stream_variant(int v) {
 
 // grad_flags: bit 0 = grad is bf16 (else fp32); bit 1 = zero the gradient
 // after reading it (the next step's zero_grad pass, fused).
-static int adamw_launch(float* master, bf16_t* param, void* grad, int grad_flags, float* m, float* v, int64_t n,
+template <typename MT>
+static int adamw_launch(float* master, bf16_t* param, void* grad, int grad_flags, MT* m, MT* v, int64_t n,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
-                        const float* norm_sq, float max_norm, const int* step_dev, hipStream_t stream) {
+                        const float* norm_sq, float max_norm, const int* step_dev, int64_t base, uint32_t seed,
+                        hipStream_t stream) {
   if (n % 8 != 0) return (int)hipErrorInvalidValue;
   const int64_t n8 = n / 8;
   const float bc1 = 1.f - powf(beta1, (float)step);
@@ -372,10 +503,11 @@ static int adamw_launch(float* master, bf16_t* param, void* grad, int grad_flags
   // non-temporal only for sweeps far beyond the caches: a small model's whole
   // optimizer state (MNIST: 2.2 MB) stays L2-resident between graph replays; 8M+ parameters per launch
   const bool nt = (g_stream_variant & 1) && n8 >= (int64_t)(1 << 20);
-  auto k = (grad_flags & 1) ? (nt ? adamw_flat_kernel<true, true> : adamw_flat_kernel<true, false>)
-                            : (nt ? adamw_flat_kernel<false, true> : adamw_flat_kernel<false, false>);
+  auto k = (grad_flags & 1) ? (nt ? adamw_flat_kernel<true, true, MT> : adamw_flat_kernel<true, false, MT>)
+                            : (nt ? adamw_flat_kernel<false, true, MT> : adamw_flat_kernel<false, false, MT>);
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, stream, master, param, grad, zero_grad, m, v, n8, lr, beta1, beta2,
-                     eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale, norm_sq, max_norm, step_dev);
+                     eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale, norm_sq, max_norm, step_dev, step, base,
+                     seed);
   return (int)hipGetLastError();
 }
 
@@ -384,7 +516,38 @@ extern "C" int toa_adamw_flat(float* master, bf16_t* param, void* grad, int grad
                               float weight_decay, int step, float grad_scale, const float* norm_sq,
                               float max_norm, hipStream_t stream) {
   return adamw_launch(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                      norm_sq, max_norm, nullptr, stream);
+                      norm_sq, max_norm, nullptr, 0, 0u, stream);
+}
+
+// bf16 moments, stochastically rounded (sr_bf16 above).  `base` is the flat
+// index of the launch's first element (a multiple of 8) and `seed` the
+// optimizer's: the rounding bits depend on (seed, step, base + local index)
+// only, never on how the flat buffer is cut into launches.
+static bool bf16s_args_ok(const void* master, const void* param, const void* grad, const void* m, const void* v,
+                          int64_t n, int64_t base) {
+  return n > 0 && n % 8 == 0 && base >= 0 && base % 8 == 0 && !((uintptr_t)master & 15) && !((uintptr_t)param & 15) &&
+         !((uintptr_t)grad & 15) && !((uintptr_t)m & 15) && !((uintptr_t)v & 15);
+}
+
+extern "C" int toa_adamw_flat_bf16s(float* master, bf16_t* param, void* grad, int grad_flags, bf16_t* m, bf16_t* v,
+                                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                    int step, float grad_scale, const float* norm_sq, float max_norm, int64_t base,
+                                    uint32_t seed, hipStream_t stream) {
+  if (!bf16s_args_ok(master, param, grad, m, v, n, base) || step < 1) return (int)hipErrorInvalidValue;
+  return adamw_launch(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                      norm_sq, max_norm, nullptr, base, seed, stream);
+}
+
+// ... with the step (bias corrections AND rounding bits) read from
+// step_dev[0]: a replayed graph draws fresh bits every step.
+extern "C" int toa_adamw_flat_bf16s_dstep(float* master, bf16_t* param, void* grad, int grad_flags, bf16_t* m,
+                                          bf16_t* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                          float weight_decay, const int* step_dev, float grad_scale,
+                                          const float* norm_sq, float max_norm, int64_t base, uint32_t seed,
+                                          hipStream_t stream) {
+  if (!bf16s_args_ok(master, param, grad, m, v, n, base) || step_dev == nullptr) return (int)hipErrorInvalidValue;
+  return adamw_launch(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay, 1, grad_scale,
+                      norm_sq, max_norm, step_dev, base, seed, stream);
 }
 
 // Same update with the step count read from device memory (step_dev[0], the
@@ -396,7 +559,7 @@ extern "C" int toa_adamw_flat_dstep(float* master, bf16_t* param, void* grad, in
                                     hipStream_t stream) {
   if (step_dev == nullptr) return (int)hipErrorInvalidValue;
   return adamw_launch(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay, 1, grad_scale,
-                      norm_sq, max_norm, step_dev, stream);
+                      norm_sq, max_norm, step_dev, 0, 0u, stream);
 }
 
 __global__ void step_inc_kernel(int* step) { step[0] += 1; }

@@ -35,6 +35,9 @@ def main(argv=None):
     p.add_argument("--fixed-batch", action="store_true", help="reuse one resident batch (benchmarking)")
     p.add_argument("--zero", choices=("auto", "0", "1"), default="auto",
                    help="ZeRO-1 sharded optimizer; auto = on for world > 1 (bench.py's default)")
+    p.add_argument("--adam-state", choices=("fp32", "bf16"), default=None,
+                   help="AdamW moment storage; bf16 = stochastically rounded, 4 B/parameter less state "
+                        "(default: TOA_ADAM_STATE, else fp32)")
     a = p.parse_args(argv)
     from tf_operator_amd.ops import gemm
 
@@ -63,7 +66,8 @@ def _train(a, rt, info):
     # (TOA_DIST_BACKEND=gloo: replicas sharing one GPU, device tensors over gloo)
     dev = pick_device() if info.backend != "gloo" or os.environ.get("TOA_DIST_BACKEND") else torch.device("cpu")
     zero = rt.world > 1 if a.zero == "auto" else a.zero == "1"
-    tr = LlamaTrainer(a.model, dev, micro_batch=a.micro_batch, seq_len=a.seq_len, lr=a.lr, shard_optimizer=zero)
+    tr = LlamaTrainer(a.model, dev, micro_batch=a.micro_batch, seq_len=a.seq_len, lr=a.lr, shard_optimizer=zero,
+                      adam_state=a.adam_state)
     rt.mark("model_init")
     tr.on_phase = rt.mark  # the first step's host-side issue points, in the start-up phases
     ck = sharded_ckpt.Checkpointer(rt.ckpt_dir, rt.rank, rt.world) if rt.ckpt_dir else None

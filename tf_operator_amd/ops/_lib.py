@@ -38,6 +38,13 @@ _SIGS = {
     "toa_adamw_flat": [c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_p, c_f, c_p],
     "toa_adamw_flat_dstep": [c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_p, c_f,
                              c_p],
+    # bf16 moments: the fp32 forms' arguments, then the flat base index and the seed before the stream
+    "toa_adamw_flat_bf16s": [c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_p, c_f,
+                             c_i64, ctypes.c_uint32, c_p],
+    "toa_adamw_flat_bf16s_dstep": [c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_p, c_f,
+                                   c_i64, ctypes.c_uint32, c_p],
+    "toa_adamw_wt_bf16s": [c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_int,
+                           c_f, c_p, c_f, c_i64, ctypes.c_uint32, c_p],
     "toa_norm_set_fwd_cap": [c_int],
     "toa_lastline_arm": [ctypes.c_char_p, c_i64, c_i64, c_int],
     "toa_lastline_disarm": [],

@@ -31,18 +31,90 @@ def grad_norm_sq(flat_grad: torch.Tensor, workspace=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------
+# bf16 moments: stochastic rounding, the integer mirror of csrc/hip/optim.hip
+# (mix32 / sr_hash / sr_bf16).  uint32 values are carried in int64 tensors;
+# an int64 product wraps, and its low 32 bits are the uint32 product.
+# ---------------------------------------------------------------------------
+_U32 = 0xFFFFFFFF
+_STATE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
+
+
+def _mix32(h: torch.Tensor) -> torch.Tensor:
+    """murmur3's finaliser on uint32 values held in an int64 tensor."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _U32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _U32
+    return h ^ (h >> 16)
+
+
+def sr_hash_reference(seed: int, step: int, index: torch.Tensor) -> torch.Tensor:
+    """The 32-bit draw of flat element `index` (int64 tensor) at `step` under
+    `seed`, as an int64 tensor in [0, 2^32): its low 16 bits round m, its
+    high 16 bits round v."""
+    key = (0x9E3779B9 * int(step) + int(seed)) & _U32
+    index = index.to(torch.int64)
+    inner = _mix32((((index >> 32) & _U32) + key) & _U32)
+    return _mix32((index & _U32) ^ inner)
+
+
+def sr_bf16_reference(x: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """fp32 `x` (bits u) rounded to bf16 with the 16-bit `r`: bits
+    (u + r) >> 16 where x is finite, u >> 16 otherwise (a NaN kept a NaN)."""
+    u = x.contiguous().view(torch.int32).to(torch.int64) & _U32
+    r = r.to(torch.int64) & 0xFFFF
+    finite = (u & 0x7F800000) != 0x7F800000
+    quiet = ((u & 0x007FFFFF) != 0).to(torch.int64) * 0x40
+    b = torch.where(finite, (u + r) >> 16, (u >> 16) | quiet)
+    b = torch.where(b >= 0x8000, b - 0x10000, b).to(torch.int16)
+    return b.view(torch.bfloat16)
+
+
+def sr_round_moments(m32, v32, base: int, step: int, seed: int):
+    """(m, v) in bf16 from their fp32 values: element j has flat index
+    base + j."""
+    idx = torch.arange(base, base + m32.numel(), dtype=torch.int64, device=m32.device).view(m32.shape)
+    h = sr_hash_reference(seed, step, idx)
+    return sr_bf16_reference(m32, h & 0xFFFF), sr_bf16_reference(v32, h >> 16)
+
+
+def moment_to_bf16(t32, key: str, base: int, seed: int):
+    """An fp32 moment piece (`key`: exp_avg / exp_avg_sq) whose first element
+    has flat index `base`, as bf16: sr_bf16 with the draw of step 0, so a
+    restore at any world size gives identical bits."""
+    t32 = t32.reshape(-1)
+    out = torch.empty(t32.numel(), dtype=torch.bfloat16, device=t32.device)
+    for c in range(0, t32.numel(), 1 << 24):   # bounded int64 temporaries
+        x = t32[c:c + (1 << 24)].float()
+        idx = torch.arange(base + c, base + c + x.numel(), dtype=torch.int64, device=x.device)
+        h = sr_hash_reference(seed, 0, idx)
+        out[c:c + x.numel()] = sr_bf16_reference(x, (h & 0xFFFF) if key == "exp_avg" else (h >> 16))
+    return out
+
+
 def adamw_reference(master, grad, m, v, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0,
-                    norm_sq=None, max_norm=0.0):
+                    norm_sq=None, max_norm=0.0, base=0, seed=0):
+    """bf16 `m` / `v`: upcast, the fp32 update, then stochastic rounding with
+    the draw of flat elements base, base + 1, ... (the weights move by the
+    unrounded moments, as in the kernels)."""
     g = grad.float() * grad_scale
     if norm_sq is not None and max_norm > 0:
         nrm = float(norm_sq.sqrt()) * grad_scale
         g = g * min(1.0, max_norm / (nrm + 1e-6))
+    m_out, v_out = m, v
+    if m.dtype == torch.bfloat16:
+        m, v = m.float(), v.float()
     m.mul_(beta1).add_(g, alpha=1 - beta1)
     v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
     bc1 = 1 - beta1 ** step
     bc2 = 1 - beta2 ** step
     denom = v.sqrt() / math.sqrt(bc2) + eps
     master.add_(-lr * (m / bc1) / denom - lr * weight_decay * master)
+    if m_out is not m:
+        mb, vb = sr_round_moments(m, v, base, step, seed)
+        m_out.copy_(mb)
+        v_out.copy_(vb)
 
 
 _MASKED = []   # (ExternalStream, handle): kept for the process's life
@@ -85,11 +157,23 @@ class FlatAdamW:
     owned=[(lo, hi), ...] (sharded data parallelism, parallel/zero.py): only
     those flat ranges are updated; the clipping norm is the all-reduced sum
     (over `group`) of the owned ranges' squared norms.  The caller zeroes
-    the gradients (the not-owned ranges hold this rank's unreduced ones)."""
+    the gradients (the not-owned ranges hold this rank's unreduced ones).
+
+    state_dtype=torch.bfloat16: exp_avg / exp_avg_sq are kept in bf16 (the
+    master stays fp32): 20 instead of 28 B of traffic and 4 B less state per
+    parameter.  After each fp32 update they are rounded stochastically
+    (sr_bf16_reference) with a counter hash of (seed, step, flat index), so
+    they stay unbiased where round-to-nearest would stall (v at beta2 =
+    0.999), and resume, sharded and W^T-writing updates stay bit-for-bit
+    (docs/kernels.md "bf16 moments")."""
 
     def __init__(self, flat, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=1.0,
                  overlap=False, buckets=None, fuse_zero_grad=False, post_update=None, owned=None, group=None,
-                 device_step=False):
+                 device_step=False, state_dtype=torch.float32, seed=0):
+        if state_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"state_dtype must be torch.float32 or torch.bfloat16, not {state_dtype!r}")
+        self.state_dtype = state_dtype
+        self.seed = int(seed) & _U32
         self.post_update = post_update
         self.sumsq = None   # an ops.gemm.SumsqSession (set by the trainer): the clipping norm from kernel partials
         # fused_wt: an ops.wt.TransposedWeights whose 2-D weights (R, C multiples of 128) the update writes
@@ -113,9 +197,12 @@ class FlatAdamW:
         self.weight_decay = weight_decay
         self.max_grad_norm = max_grad_norm
         self.step_count = 0
-        if flat.exp_avg is None:  # sized to the fp32 state this rank holds (all, or its ZeRO shards)
-            flat.exp_avg = torch.zeros(flat.state_numel, device=flat.device, dtype=torch.float32)
-            flat.exp_avg_sq = torch.zeros(flat.state_numel, device=flat.device, dtype=torch.float32)
+        # a later load allocates and converts moments in this dtype (FlatParams.load_state_shards)
+        flat.moment_dtype, flat.moment_seed = state_dtype, self.seed
+        if flat.exp_avg is None:  # sized to the state this rank holds (all, or its ZeRO shards)
+            flat.exp_avg = torch.zeros(flat.state_numel, device=flat.device, dtype=state_dtype)
+            flat.exp_avg_sq = torch.zeros(flat.state_numel, device=flat.device, dtype=state_dtype)
+        self._convert_moments()
         # without weight decay the decay split is moot: one launch over the whole buffer
         self.runs = flat.decay_runs() if weight_decay else [[0, flat.numel, False]]
         self._norm = torch.zeros(1, device=flat.device, dtype=torch.float32)
@@ -140,20 +227,45 @@ class FlatAdamW:
             self.waited = [True] * len(ranges)
             self.done = None
 
+    @torch.no_grad()
+    def _convert_moments(self):
+        """Moments that exist in the other dtype (built by hand, or assigned
+        after a load) are converted once: bf16 -> fp32 is exact, fp32 -> bf16
+        is sr_bf16 with the draw of step 0 at the true flat index."""
+        f = self.flat
+        for k in ("exp_avg", "exp_avg_sq"):
+            old = getattr(f, k)
+            if old is None or old.dtype == self.state_dtype:
+                continue
+            if self.state_dtype == torch.float32:
+                setattr(f, k, old.float())
+                continue
+            new = torch.empty(old.numel(), device=old.device, dtype=torch.bfloat16)
+            for lo, hi in f.state_ranges:
+                f.state_view(new, lo, hi).copy_(moment_to_bf16(f.state_view(old, lo, hi), k, lo, self.seed))
+            setattr(f, k, new)
+
+    def _bf16_state(self) -> bool:
+        return self.flat.exp_avg.dtype == torch.bfloat16
+
     def _launch(self, a, b, decay, lr, grad_scale, clip, zero, stream):
         f = self.flat
         gflags = int(f.grad.dtype == torch.bfloat16) | (2 if zero else 0)
         pp = f.param.data_ptr() + 2 * a if f.param.dtype == torch.bfloat16 else None
-        fn, step = ("toa_adamw_flat_dstep", _lib.ptr(self._dstep)) if self.device_step else ("toa_adamw_flat",
-                                                                                             self.step_count)
-        si = f.state_index(a)  # compact fp32 state (ZeRO shards) or == a
+        bf = self._bf16_state()
+        fn = "toa_adamw_flat_bf16s" if bf else "toa_adamw_flat"
+        fn, step = (fn + "_dstep", _lib.ptr(self._dstep)) if self.device_step else (fn, self.step_count)
+        si = f.state_index(a)  # compact state (ZeRO shards) or == a
         if f.state_index(b - 1) != si + (b - a - 1):
             raise ValueError(f"update run [{a}, {b}) crosses fp32 state ranges")
+        es = f.exp_avg.element_size()
+        # bf16 moments: the rounding bits are keyed by the FLAT index a, not the compact one
+        tail = (a, self.seed, stream) if bf else (stream,)
         _lib.call(fn, f.master.data_ptr() + 4 * si, pp, f.grad.data_ptr() + f.grad.element_size() * a,
-                  gflags, f.exp_avg.data_ptr() + 4 * si, f.exp_avg_sq.data_ptr() + 4 * si, b - a, float(lr),
+                  gflags, f.exp_avg.data_ptr() + es * si, f.exp_avg_sq.data_ptr() + es * si, b - a, float(lr),
                   float(self.beta1), float(self.beta2), float(self.eps),
                   float(self.weight_decay if decay else 0.0), step, float(grad_scale),
-                  _lib.ptr(self._norm) if clip else None, float(self.max_grad_norm or 0.0), stream)
+                  _lib.ptr(self._norm) if clip else None, float(self.max_grad_norm or 0.0), *tail)
 
     def _fused_items(self) -> dict:
         """{(lo, hi): (lo, hi, param, view)} of the W^T copies the update can
@@ -162,7 +274,7 @@ class FlatAdamW:
         wt = self.fused_wt
         f = self.flat
         if (wt is None or self.owned is not None or self.device_step or f.grad.dtype != torch.bfloat16
-                or not _lib.has("toa_adamw_wt")):
+                or not _lib.has("toa_adamw_wt_bf16s" if self._bf16_state() else "toa_adamw_wt")):
             return {}
         out = {}
         for a, b, p, view in wt.items:
@@ -176,12 +288,16 @@ class FlatAdamW:
         f = self.flat
         si = f.state_index(a)
         R, C = p.shape
-        _lib.call("toa_adamw_wt", f.master.data_ptr() + 4 * si, f.param.data_ptr() + 2 * a,
-                  f.grad.data_ptr() + 2 * a, int(bool(self.fuse_zero_grad)), f.exp_avg.data_ptr() + 4 * si,
-                  f.exp_avg_sq.data_ptr() + 4 * si, _lib.ptr(view), view.stride(0), R, C, float(lr),
+        bf = self._bf16_state()
+        es = f.exp_avg.element_size()
+        tail = (a, self.seed, stream) if bf else (stream,)
+        _lib.call("toa_adamw_wt_bf16s" if bf else "toa_adamw_wt", f.master.data_ptr() + 4 * si,
+                  f.param.data_ptr() + 2 * a,
+                  f.grad.data_ptr() + 2 * a, int(bool(self.fuse_zero_grad)), f.exp_avg.data_ptr() + es * si,
+                  f.exp_avg_sq.data_ptr() + es * si, _lib.ptr(view), view.stride(0), R, C, float(lr),
                   float(self.beta1), float(self.beta2), float(self.eps), float(self.weight_decay if decay else 0.0),
                   self.step_count, float(grad_scale), _lib.ptr(self._norm) if clip else None,
-                  float(self.max_grad_norm or 0.0), stream)
+                  float(self.max_grad_norm or 0.0), *tail)
 
     def _work_runs(self):
         """(a, b, decay) runs this rank updates."""
@@ -304,7 +420,7 @@ class FlatAdamW:
                                 beta1=self.beta1, beta2=self.beta2, eps=self.eps,
                                 weight_decay=self.weight_decay if decay else 0.0, step=self.step_count,
                                 grad_scale=grad_scale, norm_sq=self._norm if clip else None,
-                                max_norm=self.max_grad_norm or 0.0)
+                                max_norm=self.max_grad_norm or 0.0, base=a, seed=self.seed)
             for lo, hi in (self.owned or [(0, f.numel)]):
                 f.param[lo:hi].copy_(f.state_view(f.master, lo, hi).to(f.param.dtype))
             if self.post_update is not None:
@@ -332,7 +448,7 @@ class FlatAdamW:
                                     beta2=self.beta2, eps=self.eps,
                                     weight_decay=self.weight_decay if decay else 0.0, step=self.step_count,
                                     grad_scale=grad_scale, norm_sq=self._norm if clip else None,
-                                    max_norm=self.max_grad_norm or 0.0)
+                                    max_norm=self.max_grad_norm or 0.0, base=a2, seed=self.seed)
             if not hip or f.param.dtype != torch.bfloat16:
                 f.param[lo:hi].copy_(f.state_view(f.master, lo, hi).to(f.param.dtype))
             if after is not None:
@@ -345,13 +461,23 @@ class FlatAdamW:
         return self.step_count
 
     def state_dict(self):
-        return {"step": self.sync_step_count(), "lr": self.lr}
+        return {"step": self.sync_step_count(), "lr": self.lr, "seed": self.seed,
+                "state_dtype": "bfloat16" if self.state_dtype == torch.bfloat16 else "float32"}
 
     def load_state_dict(self, sd):
+        """The saved seed is adopted (a resumed run draws the uninterrupted
+        run's rounding bits).  The saved moment dtype is informational: this
+        optimizer keeps its own, and moments restored in the other one are
+        converted (FlatParams.load_state_shards, or here)."""
         self.step_count = int(sd["step"])
         if self.device_step:
             self._dstep.fill_(self.step_count)
         self.lr = sd.get("lr", self.lr)
+        self.seed = int(sd.get("seed", self.seed)) & _U32
+        self.flat.moment_seed = self.seed
+        if sd.get("state_dtype", "float32") not in _STATE_DTYPES:
+            raise ValueError(f"optimizer state of unknown moment dtype {sd['state_dtype']!r}")
+        self._convert_moments()
 
 
 class FlatSGD:

@@ -131,6 +131,12 @@ class FlatParams:
         self.state_numel = self.numel
         self.exp_avg = None
         self.exp_avg_sq = None
+        # the dtype the optimizer keeps its moments in (FlatAdamW state_dtype
+        # sets both): a load allocates missing moments in it and converts
+        # pieces saved in the other one; the seed keys the fp32 -> bf16
+        # stochastic rounding (ops/optim.py moment_to_bf16)
+        self.moment_dtype = torch.float32
+        self.moment_seed = 0
         # callbacks run after the bf16 weights are rewritten outside the
         # optimizer (checkpoint load, broadcast): derived copies such as
         # ops.wt.TransposedWeights re-derive themselves
@@ -284,9 +290,18 @@ class FlatParams:
                                 continue
                             if getattr(self, k) is None:
                                 setattr(self, k, torch.zeros(self.state_numel, device=self.device,
-                                                             dtype=torch.float32))
+                                                             dtype=torch.float32 if k == "master"
+                                                             else self.moment_dtype))
                             piece = _as_tensor(src[src_off + p - lo:src_off + q - lo])
-                            self.state_view(getattr(self, k), p, q).copy_(piece, non_blocking=False)
+                            dst = self.state_view(getattr(self, k), p, q)
+                            if k != "master" and dst.dtype == torch.bfloat16 and piece.dtype != torch.bfloat16:
+                                # fp32 moments into a bf16 run: keyed by the flat index p, so
+                                # every world size restores the same bits (a bf16 piece into
+                                # fp32 moments is copy_'s exact upcast)
+                                from ..ops.optim import moment_to_bf16
+
+                                piece = moment_to_bf16(piece.to(dst.device), k, p, self.moment_seed)
+                            dst.copy_(piece, non_blocking=False)
                         covered.append((p, q))
                 if set_params == "all" and sh.get("master") is not None:
                     for p, q in _uncovered(lo, hi, pcovered):

@@ -127,9 +127,10 @@ class ParamGather:
 
 @torch.no_grad()
 def gather_full_state(flat, world, group=None):
-    """{master, exp_avg, exp_avg_sq}: full-size fp32 tensors assembled from
-    every rank's compact shards.  Collective: every rank must call it (every
-    rank holds equally many elements: 1/world of each bucket)."""
+    """{master, exp_avg, exp_avg_sq}: full-size tensors, each in its own dtype
+    (fp32; bf16 moments stay bf16), assembled from every rank's compact
+    shards.  Collective: every rank must call it (every rank holds equally
+    many elements: 1/world of each bucket)."""
     out = {}
     ranges = torch.tensor([x for r in flat.state_ranges for x in r], dtype=torch.int64, device=flat.device)
     all_ranges = [torch.empty_like(ranges) for _ in range(world)]

@@ -33,9 +33,17 @@ from ..parallel.zero import ParamGather
 class LlamaTrainer:
     def __init__(self, cfg: LlamaConfig | str, device, micro_batch=1, seq_len=4096, grad_accum=1, lr=3e-4,
                  seed=0, bucket_mb=None, overlap_optimizer=None, shard_optimizer=None,
-                 transposed_weights=None, force_collectives=False):
+                 transposed_weights=None, force_collectives=False, adam_state=None):
         if isinstance(cfg, str):
             cfg = PRESETS[cfg]
+        # adam_state: "fp32" or "bf16" AdamW moments (None: TOA_ADAM_STATE, default fp32).  bf16 halves
+        # the moments' traffic and footprint; stochastically rounded (ops/optim.py FlatAdamW state_dtype)
+        if adam_state is None:
+            adam_state = os.environ.get("TOA_ADAM_STATE", "fp32")
+        if adam_state not in ("fp32", "bf16"):
+            raise ValueError(f"adam_state / TOA_ADAM_STATE must be 'fp32' or 'bf16', not {adam_state!r}")
+        self.adam_state = adam_state
+        state_dtype = torch.bfloat16 if adam_state == "bf16" else torch.float32
         self.cfg = cfg
         self.device = device
         self.micro_batch = micro_batch
@@ -78,7 +86,7 @@ class LlamaTrainer:
             # fp32 master / m / v only for the owned shards: 12 B/param x (1 - 1/world) of HBM freed
             self.flat.shard_state(self.bucketer.owned)
             self.bucketer.pull_rs = self._pull_reduce()
-            self.opt = FlatAdamW(self.flat, lr=lr, owned=self.bucketer.owned)
+            self.opt = FlatAdamW(self.flat, lr=lr, owned=self.bucketer.owned, state_dtype=state_dtype)
             self.gather = ParamGather(self.flat, self.bucketer.buckets, self.bucketer.rank, self.bucketer.world,
                                       on_gathered=self.wt.refresh if self.wt else None, emulator=self.bucketer.emu,
                                       pull=self._pull_gather())
@@ -87,7 +95,7 @@ class LlamaTrainer:
                 overlap_optimizer = os.environ.get("TOA_OPT_OVERLAP", "0") == "1"
             self.opt = FlatAdamW(self.flat, lr=lr, overlap=overlap_optimizer, buckets=self.bucketer.buckets,
                                  fuse_zero_grad=not self.fresh_grads,
-                                 post_update=self.wt.refresh if self.wt else None)
+                                 post_update=self.wt.refresh if self.wt else None, state_dtype=state_dtype)
             if self.wt is not None and os.environ.get("TOA_ADAM_WT", "1") != "0":
                 # the update writes the W^T copies itself (ops/optim.py toa_adamw_wt)
                 self.opt.fused_wt = self.wt

@@ -10,7 +10,8 @@ termination grace period.  Here:
 
 * **every rank saves its own share** -- the fp32 master / m / v ranges it
   holds (1/world of them under ZeRO-1, parallel/zero.py) -- as raw
-  little-endian fp32 files, no pickle;
+  little-endian fp32 files (bf16 moments: raw 16-bit words, ``.bf16``), no
+  pickle;
 * **asynchronously**: :meth:`Checkpointer.save` enqueues device -> pinned host
   copies on the current stream (stream-ordered before the next optimizer
   step; ~50 GB/s) and returns; a background thread waits for them and
@@ -48,12 +49,31 @@ import re
 import shutil
 import threading
 import time
+import warnings
 
 import numpy as np
 import torch
 
 STATE_KEYS = ("master", "exp_avg", "exp_avg_sq")
 _STEP_RE = re.compile(r"step_(\d{8})")
+# marker dtype name -> (file extension, bytes per element).  bf16 moments
+# (FlatAdamW state_dtype=bf16) are raw 16-bit words: numpy has no bf16.
+_FILE_KINDS = {"float32": ("f32", 4), "bfloat16": ("bf16", 2)}
+
+
+def _dtype_name(t: torch.Tensor) -> str:
+    if t.dtype == torch.float32:
+        return "float32"
+    if t.dtype == torch.bfloat16:
+        return "bfloat16"
+    raise TypeError(f"checkpoint state must be fp32 or bf16, not {t.dtype}")
+
+
+def _raw_array(buf: torch.Tensor) -> np.ndarray:
+    """The staged tensor's bytes as a numpy array (bf16 as uint16 words)."""
+    if buf.dtype == torch.bfloat16:
+        return buf.view(torch.int16).numpy().view(np.uint16)
+    return buf.numpy()
 
 
 def _step_dir(root: str, step: int, partial=False) -> str:
@@ -177,7 +197,8 @@ class Checkpointer:
         meta = {"rank": self.rank, "world": self.world, "step": int(step),
                 "state_ranges": [list(map(int, r)) for r in fl["state_ranges"]], "numel": int(fl["numel"]),
                 "layout": [list(x) for x in fl["layout"]], "opt": state.get("opt") or {},
-                "dtype": {k: "float32" for k in staged}, "extra": extra or {}, "attempt": self.attempt,
+                "dtype": {k: _dtype_name(b) for k, b in staged.items()}, "extra": extra or {},
+                "attempt": self.attempt,
                 "rng": {k: _b64(v) for k, v in (state.get("rng") or {}).items()}, "data": state.get("data")}
         self._error = None
         self._thread = threading.Thread(target=self._write, args=(int(step), staged, ev, meta, t0),
@@ -202,9 +223,9 @@ class Checkpointer:
             files = {}
             threads = []
             for k, buf in staged.items():
-                fn = f"rank{self.rank:05d}.{k}.f32"
+                fn = f"rank{self.rank:05d}.{k}.{_FILE_KINDS[meta['dtype'][k]][0]}"
                 files[k] = fn
-                arr = buf.numpy()
+                arr = _raw_array(buf)
                 th = threading.Thread(target=_write_raw, args=(os.path.join(d, fn), arr))
                 th.start()
                 threads.append(th)
@@ -233,9 +254,10 @@ class Checkpointer:
         if m.get("attempt") != self.attempt:
             return None
         n = sum(hi - lo for lo, hi in m["state_ranges"])
-        for fn in m.get("files", {}).values():
+        for k, fn in m.get("files", {}).items():
+            width = _FILE_KINDS.get((m.get("dtype") or {}).get(k, "float32"), (None, 4))[1]
             try:
-                if os.path.getsize(os.path.join(d, fn)) != 4 * n:
+                if os.path.getsize(os.path.join(d, fn)) != width * n:
                     return None
             except OSError:
                 return None
@@ -326,9 +348,14 @@ def load_latest(root: str | None):
         flat = {"state_ranges": [tuple(r) for r in sh["state_ranges"]], "numel": man["numel"],
                 "layout": man["layout"]}
         for k, fn in sh["files"].items():
-            arr = np.memmap(os.path.join(d, fn), dtype=np.float32, mode="r")
+            bf16 = fn.endswith(".bf16")
+            arr = np.memmap(os.path.join(d, fn), dtype=np.uint16 if bf16 else np.float32, mode="r")
             if arr.shape[0] != n:
                 raise ValueError(f"{fn}: {arr.shape[0]} elements, manifest says {n}")
+            if bf16:  # raw 16-bit words: a tensor over the mapping, viewed as bf16 (read-only: only ever read)
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    arr = torch.from_numpy(arr).view(torch.bfloat16)
             flat[k] = arr
         out.append({"flat": flat, "opt": man["opt"], "step": man["step"], "rank": sh["rank"],
                     "world": man["world"], "extra": man.get("extra", {}),

@@ -300,3 +300,55 @@ extern "C" int toa_copy_nocu(const void* src, void* dst, int64_t nbytes, hipStre
   if (nbytes <= 0) return 0;
   return (int)hipMemcpyAsync(dst, src, (size_t)nbytes, hipMemcpyDeviceToDeviceNoCU, stream);
 }
+
+// ---------------------------------------------------------------------------
+// Checking the ZeRO-1 gather waits (parallel/zero.py ParamGather with
+// TOA_ZERO_POISON / TOA_ZERO_AG_DELAY_US; docs/architecture.md).  Two
+// instruments that make a forward which reads a weight before its bucket's
+// all-gather was waited for fail every time instead of now and then:
+// the shards a rank does not own are overwritten with NaN before the gather
+// that refills them starts, and the gather is held back by a bounded wait.
+// ---------------------------------------------------------------------------
+#define TOA_DELAY_CAP_US 100000u
+// one loop turn of delay_us_kernel sleeps 32 x 64 cycles: at least 0.85 us at
+// the 2.4 GHz peak engine clock, so the cap needs fewer than 118 k turns; four
+// turns per microsecond of the cap leave a wave that reads a stuck clock after
+// about a second at the most
+#define TOA_DELAY_MAX_TURNS (4u * TOA_DELAY_CAP_US)
+
+// vectors [0, n8) of 8 bf16 each: the first a8 lie in front of the owned
+// range, the rest behind it (own8 vectors are skipped)
+__global__ __launch_bounds__(256) void zero_poison_kernel(u32x4* __restrict__ p, int64_t a8, int64_t own8, int64_t n8) {
+  const u32x4 nan8 = {0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u};  // bf16 quiet NaN x 8
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x)
+    p[i < a8 ? i : i + own8] = nan8;
+}
+
+// param[lo, hi) except [own_lo, own_hi) <- bf16 quiet NaN.  Every bound a
+// multiple of 8 elements (parallel/zero.feasible), lo <= own_lo <= own_hi <= hi.
+extern "C" int toa_zero_poison(bf16_t* param, int64_t lo, int64_t hi, int64_t own_lo, int64_t own_hi,
+                               hipStream_t stream) {
+  if (!param || ((uintptr_t)param & 15) || ((lo | hi | own_lo | own_hi) & 7) || lo < 0 || own_lo < lo ||
+      own_hi < own_lo || hi < own_hi)
+    return (int)hipErrorInvalidValue;
+  const int64_t a8 = (own_lo - lo) / 8, own8 = (own_hi - own_lo) / 8, n8 = (hi - lo) / 8 - own8;
+  if (n8 <= 0) return 0;  // the owned range is the whole range (world 1)
+  hipLaunchKernelGGL(zero_poison_kernel, dim3(toa_stream_grid(n8, 256)), dim3(256), 0, stream, (u32x4*)(param + lo),
+                     a8, own8, n8);
+  return (int)hipGetLastError();
+}
+
+// one wave: leaves once the 100 MHz wall clock advanced by `ticks`, or after
+// max_turns loop turns whatever the clock reads
+__global__ void delay_us_kernel(long long ticks, unsigned max_turns) {
+  const long long t0 = wall_clock64();
+  for (unsigned i = 0; i < max_turns && wall_clock64() - t0 < ticks; ++i) __builtin_amdgcn_s_sleep(32);
+}
+
+// Hold `stream` for `us` microseconds (the late gather of TOA_ZERO_AG_DELAY_US).
+extern "C" int toa_delay_us(unsigned us, hipStream_t stream) {
+  if (us > TOA_DELAY_CAP_US) return (int)hipErrorInvalidValue;
+  if (us == 0) return 0;
+  hipLaunchKernelGGL(delay_us_kernel, dim3(1), dim3(64), 0, stream, (long long)us * 100ll, TOA_DELAY_MAX_TURNS);
+  return (int)hipGetLastError();
+}

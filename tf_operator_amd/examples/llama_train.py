@@ -38,6 +38,8 @@ def main(argv=None):
     p.add_argument("--adam-state", choices=("fp32", "bf16"), default=None,
                    help="AdamW moment storage; bf16 = stochastically rounded, 4 B/parameter less state "
                         "(default: TOA_ADAM_STATE, else fp32)")
+    p.add_argument("--zero-check", action="store_true", default=None,
+                   help="raise on a weight read whose ZeRO-1 all-gather was not waited for (default: TOA_ZERO_CHECK)")
     a = p.parse_args(argv)
     from tf_operator_amd.ops import gemm
 
@@ -67,7 +69,7 @@ def _train(a, rt, info):
     dev = pick_device() if info.backend != "gloo" or os.environ.get("TOA_DIST_BACKEND") else torch.device("cpu")
     zero = rt.world > 1 if a.zero == "auto" else a.zero == "1"
     tr = LlamaTrainer(a.model, dev, micro_batch=a.micro_batch, seq_len=a.seq_len, lr=a.lr, shard_optimizer=zero,
-                      adam_state=a.adam_state)
+                      adam_state=a.adam_state, zero_check=a.zero_check)
     rt.mark("model_init")
     tr.on_phase = rt.mark  # the first step's host-side issue points, in the start-up phases
     ck = sharded_ckpt.Checkpointer(rt.ckpt_dir, rt.rank, rt.world) if rt.ckpt_dir else None

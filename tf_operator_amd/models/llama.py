@@ -28,6 +28,7 @@ from ..ops.embedding import Embedding
 from ..ops.linear import linear
 from ..ops.llm import (attention_block, cross_entropy, rope_cossin, rope_tables, swiglu_mlp, swiglu_mlp_resadd_ok)
 from ..ops.norm import RMSNorm
+from ..parallel.zero_check import reading
 
 
 @dataclasses.dataclass
@@ -173,7 +174,9 @@ class Llama(torch.nn.Module):
         for blk in self.blocks:
             h, delta = blk(h, delta, cos, sin, B, S, cossin)
         _, x = self.norm.presummed(h) if delta is PRESUMMED else self.norm(h, delta)
-        logits = linear(x, self.head_weight())
+        head = self.head_weight()
+        reading(head, "lm_head")   # waited for by the final norm's hook (train/llm.py _install_param_waits)
+        logits = linear(x, head)
         if targets is None:
             return logits.view(B, S, -1)
         return cross_entropy(logits, targets.reshape(-1), inplace_grad=True)

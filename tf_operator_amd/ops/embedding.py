@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ..parallel.zero_check import reading
 from .grad import deliver_weight_grad, take_fresh
 
 
@@ -25,6 +26,7 @@ def _scatter_rows(grad, idx, dy2):
 class _EmbeddingFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tokens, weight):
+        reading(weight, "embedding")
         ctx.save_for_backward(tokens)
         ctx.wshape = weight.shape
         ctx.weight = weight

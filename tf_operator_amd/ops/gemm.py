@@ -48,6 +48,7 @@ import weakref
 import torch
 
 from . import _lib
+from ..parallel.zero_check import reading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 TABLE = os.path.join(_HERE, "gemm_tuning_gfx950.json")
@@ -304,6 +305,7 @@ def asm_takes(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> bool:
 
 
 def linear_fwd(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    reading(w, "linear_fwd")
     if asm_takes(x2, w):
         M, N = x2.shape[0], w.shape[0]
         y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
@@ -329,6 +331,7 @@ def linear_resadd(x2: torch.Tensor, w: torch.Tensor, r2: torch.Tensor) -> torch.
     (toa_gemm_asm_resadd: the fp32 sum rounded to bf16 once); r2 [M, N] bf16,
     contiguous.  For operands ops.llm's ``*_resadd_ok`` predicates passed:
     anything the launcher refuses raises."""
+    reading(w, "linear_resadd")
     y = torch.empty_like(r2)
     _lib.call("toa_gemm_asm_resadd", _lib.ptr(x2), x2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(y), y.stride(0),
               _lib.ptr(r2), x2.shape[0], w.shape[0], x2.shape[1], _lib.stream(x2))
@@ -393,6 +396,7 @@ def nn_takes(dy2: torch.Tensor, w: torch.Tensor) -> bool:
 
 
 def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    reading(w, "linear_dgrad")   # the W^T copy is refreshed by the gather's wait: a read of it is a read of w
     wt = getattr(w, "_toa_wt", None)
     if wt is not None:  # W^T kept by ops.wt.TransposedWeights: dx = dy (W^T)^T, the forward's form
         return linear_fwd(dy2, wt)
@@ -420,6 +424,7 @@ def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def swiglu_gate_up(x2: torch.Tensor, wgu: torch.Tensor):
     """(gu, s) = (x Wgu^T, silu(gate) * up) from ONE assembly GEMM with the
     SwiGLU in its epilogue; None when the kernel cannot take the shapes."""
+    reading(wgu, "swiglu_gate_up")
     if not (asm_takes(x2, wgu, n_mult=2) and (wgu.shape[0] // 2) % 128 == 0):
         return None
     M, F = x2.shape[0], wgu.shape[0] // 2
@@ -435,6 +440,7 @@ def swiglu_down_dgrad(d2: torch.Tensor, wd: torch.Tensor, gu: torch.Tensor):
     transposed weight copy (ops/wt.py) -- or, without one under
     ``dgrad_form() == "nn"``, on Wd as stored -- with the SwiGLU backward in
     its epilogue (ds is never stored); None when the kernel cannot take it."""
+    reading(wd, "swiglu_down_dgrad")
     wdt = getattr(wd, "_toa_wt", None)
     if wdt is None and dgrad_form() == "nn":     # on Wd [D, F] as stored (the NN form)
         if not (nn_takes(d2, wd) and _lib.has("toa_gemm_nn_asm_swiglu_bwd") and gu.is_contiguous()

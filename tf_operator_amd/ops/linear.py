@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import gemm
+from ..parallel.zero_check import reading
 from .grad import accumulate_mm
 
 
@@ -34,6 +35,7 @@ class _LinearFn(torch.autograd.Function):
 
 
 def linear(x, weight):
+    reading(weight, "linear")
     return _LinearFn.apply(x, weight)
 
 

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import gemm
+from ..parallel.zero_check import reading
 from .grad import accumulate_mm
 from .linear import linear
 
@@ -143,6 +144,7 @@ class _SwiGLUDown(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gu, wd):
+        reading(wd, "swiglu_down")
         s = swiglu(gu)
         ctx.save_for_backward(gu, wd, None if _SWIGLU_RECOMPUTE else s)
         return gemm.linear_fwd(s.reshape(-1, s.shape[-1]), wd).view(*s.shape[:-1], wd.shape[0])
@@ -150,6 +152,7 @@ class _SwiGLUDown(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         gu, wd, s = ctx.saved_tensors
+        reading(wd, "swiglu_down backward")
         if s is None:
             s = swiglu(gu)
         d2 = dout.reshape(-1, dout.shape[-1])
@@ -174,6 +177,8 @@ class _SwiGLUMLP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wgu, wd, residual=None):
+        reading(wgu, "swiglu_mlp")
+        reading(wd, "swiglu_mlp")
         x2 = x.reshape(-1, x.shape[-1])
         r = gemm.swiglu_gate_up(x2, wgu)
         gu, s = r if r is not None else (None, None)
@@ -189,6 +194,8 @@ class _SwiGLUMLP(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, wgu, wd, gu, s = ctx.saved_tensors
+        reading(wgu, "swiglu_mlp backward")
+        reading(wd, "swiglu_mlp backward")
         d2 = dout.reshape(-1, dout.shape[-1])
         dwd = accumulate_mm(wd, d2.t(), s)
         del s
@@ -441,6 +448,7 @@ class _AttnOutProj(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, o2, wo, B, S, H, residual, link):
+        reading(wo, "attn_out_proj")
         ctx.save_for_backward(o2, wo)
         ctx.dims = (B, S, H)
         ctx.has_res, ctx.link = residual is not None, link
@@ -455,6 +463,7 @@ class _AttnOutProj(torch.autograd.Function):
         B, S, H = ctx.dims
         dy2 = dy.reshape(-1, dy.shape[-1])
         dx = None
+        reading(wo, "attn_out_proj backward")   # either delta form: W^T is a copy of wo, refreshed by its gather's wait
         wt = getattr(wo, "_toa_wt", None)
         # the delta GEMM on the W^T copy, or without one under dgrad_form "nn" on wo as stored
         fn, wmat = ("toa_gemm_asm_delta", wt) if wt is not None else ("toa_gemm_nn_asm_delta", wo)
@@ -513,6 +522,7 @@ class _QKVRopeAttn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wqkv, cos, sin, cossin, B, S, Hq, Hkv, D, scale, bshd, link):
+        reading(wqkv, "qkv_rope_attention")
         x2 = x.reshape(-1, x.shape[-1])
         T, K = x2.shape
         out = torch.empty(T * (Hq + 2 * Hkv) * D, device=x.device, dtype=x.dtype)
@@ -530,6 +540,7 @@ class _QKVRopeAttn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         x, wqkv, q, k, v, o, lse, cos, sin = ctx.saved_tensors
+        reading(wqkv, "qkv_rope_attention backward")
         do = do.contiguous()
         ndelta = ctx.link.take(do) if ctx.link is not None else None
         dqkv = _rope_attn_dqkv(q, k, v, o, lse, cos, sin, do, ctx.scale, ctx.bshd, ndelta)

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ..parallel.zero_check import reading
 from .grad import deliver_weight_grad, take_fresh
 
 
@@ -47,6 +48,8 @@ def _ref_norm_bwd(dy, h, w, mean, rstd, rms):
 class _NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, eps, rms):
+        reading(weight, "norm")   # the module forward and presummed both arrive here
+        reading(bias, "norm")
         shape = x.shape
         cols = shape[-1]
         x2 = x.reshape(-1, cols)
@@ -88,6 +91,7 @@ class _NormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         h, weight, mean, rstd = ctx.saved_tensors
+        reading(weight, "norm backward")
         rms = ctx.rms
         cols = h.shape[-1]
         rows = h.shape[0]

@@ -232,12 +232,16 @@ class GpuIpcTransport:
         L = self._lib
         L.call("toa_flag_publish", ctypes.c_void_p(self._own.value + 4 * idx), epoch, L.stream(self.buf))
 
-    def pull(self, idx: int, epoch: int, pieces, dst=None):
-        """As ShmTransport.pull, on the copy stream (SDMA copies)."""
+    def pull(self, idx: int, epoch: int, pieces, dst=None, delay_us: int = 0):
+        """As ShmTransport.pull, on the copy stream (SDMA copies).  delay_us:
+        hold the copy stream that long first (the late gather of
+        TOA_ZERO_AG_DELAY_US, parallel/zero_check.py)."""
         L = self._lib
         cur = torch.cuda.current_stream(self.buf.device)
         self.stream.wait_stream(cur)   # this rank's readers of the old weights are done
         st = ctypes.c_void_p(self.stream.cuda_stream)
+        if delay_us:
+            L.call("toa_delay_us", int(delay_us), st)
         L.call("toa_flags_wait", self.flags, idx, self.rank, self.world, epoch, L.ptr(self.err), self.timeout_ms, st)
         es = self.buf.element_size()
         out = self.buf if dst is None else dst
@@ -311,10 +315,13 @@ class PullGather:
         n = (hi - lo) // self.world
         return [(r, lo + r * n, lo + (r + 1) * n) for r in range(self.world) if r != self.rank]
 
-    def launch_one(self, b):
+    def launch_one(self, b, delay_us: int = 0):
         """Bucket b's own shard is updated (on the current stream): publish
-        it and pull the peers'.  Returns a Work-like handle."""
+        it and pull the peers'.  Returns a Work-like handle.  delay_us: see
+        GpuIpcTransport.pull (the GPU transport only)."""
         self.t.publish(b, self.epoch)
+        if delay_us:
+            return self.t.pull(b, self.epoch, self.pieces(b), delay_us=delay_us)
         return self.t.pull(b, self.epoch, self.pieces(b))
 
     def check(self):

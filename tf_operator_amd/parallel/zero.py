@@ -38,6 +38,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from . import zero_check
+
 
 def feasible(buckets, world: int) -> bool:
     return world >= 1 and all((e - s) % (8 * world) == 0 for s, e, *_ in buckets)
@@ -80,7 +82,10 @@ class ParamGather:
     """In-place all-gather of the updated bf16 weights after a sharded
     optimizer step, waited for per bucket by the next forward."""
 
-    def __init__(self, flat, buckets, rank, world, group=None, on_gathered=None, emulator=None, pull=None):
+    def __init__(self, flat, buckets, rank, world, group=None, on_gathered=None, emulator=None, pull=None,
+                 check=False, poison=False, delay_us=0):
+        """check / poison / delay_us: the instruments of parallel/zero_check.py
+        (TOA_ZERO_CHECK, TOA_ZERO_POISON, TOA_ZERO_AG_DELAY_US), all off by default."""
         self.flat = flat
         self.emu = emulator  # parallel/emulate.CommEmulator: paced traffic instead of RCCL (world 1)
         self.pull = pull     # parallel/pull_gather.PullGather: copy-engine pulls instead of RCCL (TOA_ZERO_AG=sdma)
@@ -88,6 +93,48 @@ class ParamGather:
         self.rank, self.world, self.group = rank, world, group
         self.on_gathered = on_gathered  # fn(lo, hi) on the waiting stream (W^T refresh)
         self.works = [None] * len(self.ranges)
+        self.check, self.poison, self.delay_us = bool(check), bool(poison), zero_check.validate_delay_us(delay_us)
+        self._delay_stream = None  # carries the delayed RCCL gathers (never the compute stream)
+        if self.check:  # reads of these parameters go through zero_check.reading
+            per_bucket = [[] for _ in self.ranges]
+            for seg in flat.segments:
+                per_bucket[self._bucket_of(seg.offset)].append(seg.param)
+            zero_check.tag(self, per_bucket, {id(seg.param): seg.name for seg in flat.segments})
+
+    def _bucket_of(self, offset):
+        return next(b for b, (lo, hi) in enumerate(self.ranges) if lo <= offset < hi)
+
+    def _on_device(self):
+        """The device instruments apply: real traffic into a GPU buffer."""
+        return self.emu is None and self.flat.param.is_cuda
+
+    def _poison_others(self, b):
+        """NaN over the shards of bucket b this rank does not own, on the
+        current stream: it has run this step's last reader of the old weights
+        and this rank's update of its own shard, and the gather that refills
+        them is ordered behind it."""
+        from ..ops import _lib
+
+        lo, hi = self.ranges[b]
+        n = (hi - lo) // self.world
+        _lib.call("toa_zero_poison", _lib.ptr(self.flat.param), lo, hi, lo + self.rank * n, lo + (self.rank + 1) * n,
+                  _lib.stream(self.flat.param))
+
+    def _delayed_all_gather(self, view):
+        """The RCCL gather issued under a side stream that waits for the
+        current one and then sits out the delay: the collective is ordered
+        behind the delay, the compute stream is not.  work.wait() is unchanged."""
+        import ctypes
+
+        from ..ops import _lib
+
+        if self._delay_stream is None:
+            self._delay_stream = torch.cuda.Stream(device=view.device)
+        side = self._delay_stream
+        side.wait_stream(torch.cuda.current_stream(view.device))
+        _lib.call("toa_delay_us", self.delay_us, ctypes.c_void_p(side.cuda_stream))
+        with torch.cuda.stream(side):
+            return all_gather_(view, self.rank, self.world, self.group)
 
     def order(self):
         """Forward-need order: flat order is backward order, so the forward
@@ -98,12 +145,19 @@ class ParamGather:
         """All-gather bucket b (its owned shard must be updated on the
         current stream already: the collective waits for that stream)."""
         lo, hi = self.ranges[b]
+        device = self._on_device()
+        if self.poison and device:
+            self._poison_others(b)
         if self.pull is not None:
             if b == self.order()[0]:
                 self.pull.new_step()   # one epoch per optimizer step, the same on every rank
-            self.works[b] = self.pull.launch_one(b)
+            # the delay rides on the transport's copy stream, ahead of its flags wait
+            self.works[b] = (self.pull.launch_one(b, delay_us=self.delay_us) if self.delay_us and device
+                             else self.pull.launch_one(b))
         elif self.emu is not None:
             self.works[b] = self.emu.collective(self.flat.param[lo:hi], kind="all_gather")
+        elif self.delay_us and device:
+            self.works[b] = self._delayed_all_gather(self.flat.param[lo:hi])
         else:
             self.works[b] = all_gather_(self.flat.param[lo:hi], self.rank, self.world, self.group)
 

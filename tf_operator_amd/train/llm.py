@@ -26,6 +26,7 @@ from ..ops.optim import FlatAdamW
 from ..ops.wt import TransposedWeights, enabled_default
 from ..parallel.ddp import GradBucketer, broadcast_params
 from ..parallel import zero
+from ..parallel import zero_check as _zc
 from ..parallel.flat import FlatParams
 from ..parallel.zero import ParamGather
 
@@ -33,7 +34,8 @@ from ..parallel.zero import ParamGather
 class LlamaTrainer:
     def __init__(self, cfg: LlamaConfig | str, device, micro_batch=1, seq_len=4096, grad_accum=1, lr=3e-4,
                  seed=0, bucket_mb=None, overlap_optimizer=None, shard_optimizer=None,
-                 transposed_weights=None, force_collectives=False, adam_state=None):
+                 transposed_weights=None, force_collectives=False, adam_state=None, zero_check=None,
+                 zero_poison=None, zero_ag_delay_us=None):
         if isinstance(cfg, str):
             cfg = PRESETS[cfg]
         # adam_state: "fp32" or "bf16" AdamW moments (None: TOA_ADAM_STATE, default fp32).  bf16 halves
@@ -43,6 +45,13 @@ class LlamaTrainer:
         if adam_state not in ("fp32", "bf16"):
             raise ValueError(f"adam_state / TOA_ADAM_STATE must be 'fp32' or 'bf16', not {adam_state!r}")
         self.adam_state = adam_state
+        # the ZeRO-1 gather-wait instruments (parallel/zero_check.py), all off by default: zero_check
+        # (TOA_ZERO_CHECK) raises on a weight read whose bucket's all-gather was not waited for;
+        # zero_poison (TOA_ZERO_POISON) + zero_ag_delay_us (TOA_ZERO_AG_DELAY_US) make such a read give NaN
+        self.zero_check = _zc.check_from_env() if zero_check is None else bool(zero_check)
+        self.zero_poison = _zc.poison_from_env() if zero_poison is None else bool(zero_poison)
+        self.zero_ag_delay_us = _zc.validate_delay_us(_zc.ag_delay_us_from_env() if zero_ag_delay_us is None
+                                                      else zero_ag_delay_us)
         state_dtype = torch.bfloat16 if adam_state == "bf16" else torch.float32
         self.cfg = cfg
         self.device = device
@@ -89,7 +98,8 @@ class LlamaTrainer:
             self.opt = FlatAdamW(self.flat, lr=lr, owned=self.bucketer.owned, state_dtype=state_dtype)
             self.gather = ParamGather(self.flat, self.bucketer.buckets, self.bucketer.rank, self.bucketer.world,
                                       on_gathered=self.wt.refresh if self.wt else None, emulator=self.bucketer.emu,
-                                      pull=self._pull_gather())
+                                      pull=self._pull_gather(), check=self.zero_check, poison=self.zero_poison,
+                                      delay_us=self.zero_ag_delay_us)
         else:
             if overlap_optimizer is None:
                 overlap_optimizer = os.environ.get("TOA_OPT_OVERLAP", "0") == "1"
@@ -100,6 +110,7 @@ class LlamaTrainer:
                 # the update writes the W^T copies itself (ops/optim.py toa_adamw_wt)
                 self.opt.fused_wt = self.wt
         self._fused_norm(model)
+        self._hook_by_module = {}  # module name -> its wait hook's handle (the same handles as _hooks)
         if self.opt.overlap or self.gather is not None:
             self._hooks = self._install_param_waits()
         self._closed = False
@@ -170,6 +181,7 @@ class LlamaTrainer:
             if ps:
                 bs = sorted({p._toa_bucket for p in ps})
                 hooks.append(mod.register_forward_pre_hook(waiter(bs)))
+                self._hook_by_module[name] = hooks[-1]
         return hooks
 
     def synthetic_batch(self, seed=1234):

@@ -1,6 +1,6 @@
 """Kernel-argument packing for the generated assembly GEMMs, shared by the
 CPU emulator tests and documented against csrc/hip/gemm_asm.hip, which packs
-the same 80 bytes on the host side of the real launch."""
+the same 96 bytes on the host side of the real launch."""
 from __future__ import annotations
 
 import struct
@@ -62,11 +62,11 @@ def tile_order(tiles_m: int, tiles_n: int, tile_map: int = MAP_DEFAULT) -> list[
 
 
 def wgrad_plan(M: int, N: int, K: int) -> tuple[int, int]:
-    """(full, split) of csrc/hip/wgrad.hip's wg_plan: whole-K tiles for
-    whole waves of 256 CUs, the tail cut into 2..4 K-pieces that fill it.
-    A K that is no multiple of 64 (the assembly kernel only:
-    csrc/hip/gemm_asm.hip wgrad_asm_plan) takes the largest such split that
-    divides its ceil(K / 64) k-tiles: pieces are cut at multiples of 64 rows."""
+    """(full, split) of csrc/hip/gemm_asm_shapes.h's wgrad_plan (the auto
+    plan): whole-K tiles for whole waves of 256 CUs, the tail cut into 2..4
+    K-pieces that fill it.  A K that is no multiple of 64 (the assembly kernel
+    only) takes the largest such split that divides its ceil(K / 64) k-tiles:
+    pieces are cut at multiples of 64 rows."""
     tiles = (M // 256) * (N // 256)
     rem = tiles % 256
     if rem == 0:

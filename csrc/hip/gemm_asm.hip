@@ -12,18 +12,18 @@
 //   toa_gemm_asm_swiglu_bwd   dgu = SwiGLU'(gu) applied to ds = dY WdT^T
 //                             (ds never stored)                  (one launch)
 //
-// Shapes: N a multiple of 256 (F of 128 forward / 256 backward), K a
-// multiple of 64 and >= 128, row strides multiples of 8 elements, 16-byte
-// aligned bases.  M (the token count) is free for the product launchers
-// toa_gemm_asm_rows / _resadd / _swiglu / _swiglu_bwd: tiles_m = ceil(M /
-// 256) and the kernarg word `m` ends the last tile row's X / C / S resources
-// at row M, so the hardware's range check zero-fills its loads and drops its
-// stores past M.  Every other entry (toa_gemm_asm itself, whose refusal of a
-// partial tile row callers and tests rely on, the variant, timing, trace,
-// probe, persistent arms, the rope and delta epilogues) takes M % 256 == 0.
-// Anything else returns hipErrorInvalidValue before a launch (callers fall
-// back to another GEMM), so the kernel never sees a shape whose tiles it does
-// not cover.  The 96-byte argument block matches KARG in gemm_gen.py (and
+// Shapes: gemm_asm_shapes.h holds one check per form (and docs/kernels.md a
+// table of them); every entry here calls its form's check and returns
+// hipErrorInvalidValue before a launch for anything else (callers ask
+// toa_gemm_shape_check first and fall back to another GEMM), so the kernel
+// never sees a shape whose tiles it does not cover.  M (the token count) is
+// free for the product launchers toa_gemm_asm_rows / _resadd / _swiglu /
+// _swiglu_bwd: tiles_m = ceil(M / 256) and the kernarg word `m` ends the last
+// tile row's X / C / S resources at row M, so the hardware's range check
+// zero-fills its loads and drops its stores past M.  Every other TN entry
+// (toa_gemm_asm itself, whose refusal of a partial tile row callers and tests
+// rely on, the diagnostic entries, the rope and delta epilogues) takes whole
+// tiles.  The 96-byte argument block matches KARG in gemm_gen.py (and
 // csrc/asm/host_args.py, which the CPU emulator tests use).
 #include <hip/hip_runtime.h>
 
@@ -32,9 +32,12 @@
 #include <cstring>
 #include <mutex>
 
+#include "gemm_asm_shapes.h"
 #include "toa_common.h"
 
 namespace {
+
+using namespace toa_shapes;
 
 #include "toa_asm_blob.inc"  // const unsigned char toa_asm_blob[]; size_t toa_asm_blob_len
 
@@ -127,9 +130,6 @@ static_assert(sizeof(Args) == 96, "kernarg block must match csrc/asm/gemm_gen.py
 constexpr uint32_t kMapDefault = 2;  // groups of 4 row tiles walk the column tiles
 constexpr uint32_t kMapWalkCols = 16;
 
-bool ld_ok(int64_t ld, int64_t min_cols) { return ld >= min_cols && ld % 8 == 0 && ld * 2 * 256 < (1ll << 32); }
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // The plain kernel's A/B arms by variant number 1.. (gemm_gen.py
 // PLAIN_VARIANTS): kernel id, and whether it walks several tiles per
 // workgroup (SCHED "persist": its grid is one workgroup per CU).
@@ -219,11 +219,24 @@ Args base_args(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, 
   return a;
 }
 
-// m_tail: the launcher takes any M (the product launchers; see the header).
-bool common_ok(int M, int K, int64_t ldx, int64_t ldw, const void* X, const void* W, bool m_tail = false) {
-  return M > 0 && (m_tail || M % 256 == 0) && K >= 128 && K % 64 == 0 && ld_ok(ldx, K) && ld_ok(ldw, K) && al16(X) &&
-         al16(W) && (int64_t)M < (1 << 28);
+// The operand description of gemm_asm_shapes.h from a launcher's arguments
+// (S, D and the epilogues' extras are set by the entries that have them).
+Operands operands(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* C, int64_t ldc, int M, int N,
+                  int K, const void* S = nullptr, int64_t lds = 0) {
+  Operands o = {};
+  o.X = (uintptr_t)X, o.W = (uintptr_t)W, o.C = (uintptr_t)C, o.S = (uintptr_t)S;
+  o.ldx = ldx, o.ldw = ldw, o.ldc = ldc, o.lds = lds;
+  o.M = M, o.N = N, o.K = K;
+  return o;
 }
+
+// the attention epilogues' extras: -delta rows, sequence length, heads
+Operands with_delta(Operands o, const float* ndelta, int S, int H) {
+  o.D = (uintptr_t)ndelta, o.Sq = S, o.H = H;
+  return o;
+}
+
+bool takes(int form, const Operands& o) { return check(form, o) == R_OK; }
 
 }  // namespace
 
@@ -250,6 +263,18 @@ extern "C" int toa_gemm_asm_available() {
   return get_fn(K_PLAIN, &err) != nullptr ? 1 : 0;
 }
 
+// What the launchers below would say to these operands, without a device:
+// gemm_asm_shapes.h check(form, ...), 0 = taken, else the first condition that
+// fails; toa_gemm_shape_why names it.  Slots per form: see Operands there.
+extern "C" int toa_gemm_shape_check(int form, const void* X, const void* W, const void* C, const void* S,
+                                    const void* D, int64_t ldx, int64_t ldw, int64_t ldc, int64_t lds, int M, int N,
+                                    int K, int Sq, int H, int Hq, int Hkv, int split) {
+  Operands o = operands(X, ldx, W, ldw, C, ldc, M, N, K, S, lds);
+  o.D = (uintptr_t)D, o.Sq = Sq, o.H = H, o.Hq = Hq, o.Hkv = Hkv, o.split = split;
+  return (int)check(form, o);
+}
+extern "C" const char* toa_gemm_shape_why(int reason) { return why(reason); }
+
 // Persistent plain kernel (PLAIN_VARIANTS v3: a workgroup per CU walks its
 // tiles, the next tile's first k-tiles staged under the current epilogue).
 // In isolation it is 1.5-2.8 % faster at the qkv / o forward and data-gradient
@@ -269,8 +294,7 @@ bool use_persist(int N, int K) {
 
 static int gemm_asm_plain(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc, int M,
                           int N, int K, bool m_tail, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W, m_tail) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C))
-    return (int)hipErrorInvalidValue;
+  if (!takes(m_tail ? F_TN_ROWS : F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K))) return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   if (M % 256 == 0 && use_persist(N, K)) {
     const unsigned tiles = a.tiles_m * a.tiles_n;
@@ -302,8 +326,7 @@ extern "C" int toa_gemm_asm_set_persist(int v) {
 // gemm_gen.py PLAIN_VARIANTS lists), same arguments and checks as toa_gemm_asm.
 extern "C" int toa_gemm_asm_variant(int v, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
                                     int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (v < 0 || v > kNumPlainVariants || !common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) ||
-      !al16(C) || (v == 9 && K < 192))
+  if (v < 0 || v > kNumPlainVariants || (v == 9 && K < 192) || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   if (v > 0 && kVariantPersist[v - 1]) {
@@ -317,8 +340,7 @@ extern "C" int toa_gemm_asm_variant(int v, const bf16_t* X, int64_t ldx, const b
 // tile_map) instead of the per-shape choice.
 extern "C" int toa_gemm_asm_map(int map, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
                                 int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (map < 0 || map >= 32 || (map & 15) > 6 || !common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 ||
-      !ld_ok(ldc, N) || !al16(C))
+  if (map < 0 || map >= 32 || (map & 15) > 6 || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.map = (uint32_t)map;
@@ -333,8 +355,7 @@ extern "C" int toa_gemm_asm_map(int map, const bf16_t* X, int64_t ldx, const bf1
 // stretches of the main loop.
 extern "C" int toa_gemm_asm_timing(int which, void* out, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                                    bf16_t* C, int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !out || !al16(out) ||
-      (which != 1 && which != 2))
+  if (!out || !al16(out) || (which != 1 && which != 2) || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)out;
@@ -345,7 +366,7 @@ extern "C" int toa_gemm_asm_timing(int which, void* out, const bf16_t* X, int64_
 // 2 = main loop done, 0 = everything), for bisecting a hardware fault.
 extern "C" int toa_gemm_asm_stage(int stage, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
                                   int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || stage < 0 || stage > 2)
+  if (stage < 0 || stage > 2 || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.fc = (uint32_t)stage;
@@ -367,8 +388,7 @@ extern "C" int toa_host_free(void* p) { return (int)hipHostFree(p); }
 // workgroup and wave): after a fault, how far every wave got.
 extern "C" int toa_gemm_asm_trace(void* trace_host, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                                   bf16_t* C, int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !trace_host)
-    return (int)hipErrorInvalidValue;
+  if (!trace_host || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K))) return (int)hipErrorInvalidValue;
   void* dev = nullptr;
   hipError_t e = hipHostGetDevicePointer(&dev, trace_host, 0);
   if (e != hipSuccess) return (int)e;
@@ -383,8 +403,7 @@ extern "C" int toa_gemm_asm_trace(void* trace_host, const bf16_t* X, int64_t ldx
 // argument block that arrives corrupted stores nothing.
 extern "C" int toa_gemm_asm_probe(void* out, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
                                   int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !al16(out))
-    return (int)hipErrorInvalidValue;
+  if (!al16(out) || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K))) return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)out;
   a.fw = 0x626F7270u;
@@ -403,7 +422,6 @@ extern "C" int toa_gemm_asm_probe(void* out, const bf16_t* X, int64_t ldx, const
 // cut into k-pieces), split >= 1 every tile cut into `split` pieces; the
 // pieces' fp32 partials (workspace W, toa_wgrad_workspace bytes) are summed in
 // a fixed order by wgrad.hip's reduce kernel.
-extern "C" int toa_wgrad_split(int M, int N, int K);
 extern "C" int toa_wgrad_reduce_map(const float* W, bf16_t* C, int64_t ldc, int M, int N, int full, int rem,
                                     int split, int beta, unsigned map, hipStream_t stream);
 extern "C" int toa_wgrad_reduce_map_sq(const float* W, bf16_t* C, int64_t ldc, int M, int N, int full, int rem,
@@ -452,33 +470,12 @@ extern "C" int toa_wgrad_asm_set_map(int map) {
   return 0;
 }
 
-// The auto plan's split.  K (the token count) a multiple of 64: wgrad.hip's
-// plan, shared with the HIP kernel.  Any other K (this kernel only: ceil(K /
-// 64) k-tiles, the last one staged through resources that end at row K, so
-// its rows past K read as 0): the largest split in 2..4 that fills the
-// last wave, DIVIDES the k-tiles -- pieces are cut at multiples of 64 rows, the
-// last one carries the tail -- and leaves 512 rows a piece (wgrad.hip's floor).
-// Mirrored by csrc/asm/host_args.py wgrad_plan.
-static int wgrad_asm_split(int M, int N, int K) {
-  if (K % 64 == 0) return toa_wgrad_split(M, N, K);
-  const int rem = ((M / 256) * (N / 256)) % 256, kt = (K + 63) / 64;
-  int best = 1;
-  for (int s = 2; rem && s <= 4; ++s)
-    if (rem * s <= 256 && kt % s == 0 && K / s >= 512) best = s;
-  return best;
-}
-
 // Bytes of fp32 workspace toa_wgrad_asm needs (toa_wgrad_workspace's contract
-// on this kernel's plan; equal to it wherever K % 64 == 0).
+// on this kernel's plan, gemm_asm_shapes.h wgrad_plan; equal to it wherever
+// K % 64 == 0).
 extern "C" int64_t toa_wgrad_asm_workspace(int M, int N, int K, int split) {
   if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || split < 0) return 0;
-  const int64_t tiles = (int64_t)(M / 256) * (N / 256);
-  int64_t rem = tiles;
-  if (split == 0) {
-    split = wgrad_asm_split(M, N, K);
-    rem = tiles % 256;
-  }
-  return split > 1 ? (int64_t)split * rem * 256 * 256 * 4 : 0;
+  return wgrad_workspace(M, N, K, split, true);
 }
 
 extern "C" int toa_wgrad_asm(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C, int64_t ldc,
@@ -497,23 +494,13 @@ extern "C" int toa_wgrad_asm_variant(int v, const bf16_t* A, int64_t lda, const 
 
 static int wgrad_asm_launch(int which, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C,
                             int64_t ldc, float* W, int M, int N, int K, int split, int beta, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || split < 0 || split > 4 || !ld_ok(lda, M) ||
-      !ld_ok(ldb, N) || !ld_ok(ldc, N) || !al16(A) || !al16(B) || !al16(C) || (lda * 2) * 64 >= (1ll << 31) ||
-      (ldb * 2) * 64 >= (1ll << 31))
-    return (int)hipErrorInvalidValue;
-  const int tiles = (M / 256) * (N / 256);
+  Operands o = operands(A, lda, B, ldb, C, ldc, M, N, K, W);
+  o.split = split;
+  WgradPlan plan;
+  if (check_wgrad_asm(o, &plan) != R_OK) return (int)hipErrorInvalidValue;
+  split = plan.split;
+  const int full = plan.full, rem = (M / 256) * (N / 256) - full;
   const int kt = (K + 63) / 64;   // k-tiles; K % 64 rows of the last one are live when K % 64 != 0
-  int full;
-  if (split == 0) {
-    split = wgrad_asm_split(M, N, K);
-    full = split > 1 ? tiles - tiles % 256 : tiles;
-  } else {
-    full = split == 1 ? tiles : 0;
-  }
-  const int rem = tiles - full;
-  if (kt % split || kt / split < 2 || (split > 1 && (W == nullptr || !al16(W))) ||
-      (int64_t)split * rem >= (1 << 14))
-    return (int)hipErrorInvalidValue;
   Args a;
   memset(&a, 0, sizeof(a));
   a.X = (uint64_t)A;
@@ -667,9 +654,7 @@ static int launch_swiglu(int which, int persist_bit, const Args& a, hipStream_t 
 
 extern "C" int toa_gemm_asm_swiglu(const bf16_t* X, int64_t ldx, const bf16_t* Wgu, int64_t ldw, bf16_t* GU,
                                    int64_t ldgu, bf16_t* S, int64_t lds_, int M, int F, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, Wgu, true) || F <= 0 || F % 128 || !ld_ok(ldgu, 2 * F) || !ld_ok(lds_, F) || !al16(GU) ||
-      !al16(S) || (int64_t)F * ldw * 2 + 128 * ldw * 2 >= (1ll << 32))
-    return (int)hipErrorInvalidValue;
+  if (!takes(F_TN_SWIGLU_FWD, operands(X, ldx, Wgu, ldw, GU, ldgu, M, F, K, S, lds_))) return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, Wgu, ldw, GU, ldgu, M, F / 128, K);
   a.S = (uint64_t)S;
   a.lds = (uint32_t)(lds_ * 2);
@@ -681,8 +666,7 @@ extern "C" int toa_gemm_asm_swiglu(const bf16_t* X, int64_t ldx, const bf16_t* W
 extern "C" int toa_gemm_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16_t* WdT, int64_t ldw,
                                        const bf16_t* GU, int64_t ldgu, bf16_t* dGU, int64_t lddgu, int M, int F, int K,
                                        hipStream_t stream) {
-  if (!common_ok(M, K, ldy, ldw, dY, WdT, true) || F <= 0 || F % 256 || !ld_ok(ldgu, 2 * F) || !ld_ok(lddgu, 2 * F) ||
-      !al16(GU) || !al16(dGU))
+  if (!takes(F_TN_SWIGLU_BWD, operands(dY, ldy, WdT, ldw, dGU, lddgu, M, F, K, GU, ldgu)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(dY, ldy, WdT, ldw, dGU, lddgu, M, F / 256, K);
   a.S = (uint64_t)GU;
@@ -697,12 +681,10 @@ extern "C" int toa_gemm_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16
 // fp32.  N = (Hq + 2 Hkv) 128 must be a multiple of 256, S of 256, M of S.
 extern "C" int toa_gemm_asm_rope(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* out,
                                  const float* cossin, int M, int K, int S, int Hq, int Hkv, hipStream_t stream) {
-  const int64_t N = (int64_t)(Hq + 2 * Hkv) * 128;
-  if (!common_ok(M, K, ldx, ldw, X, W) || Hq <= 0 || Hkv <= 0 || Hq > 4096 || Hkv > 4096 || N % 256 || S <= 0 ||
-      S % 256 || M % S || !al16(out) || !al16(cossin) || (int64_t)M * N * 2 >= (1ll << 32) ||
-      (int64_t)S * 512 + 128 * 256 >= (1ll << 32))
-    return (int)hipErrorInvalidValue;
-  Args a = base_args(X, ldx, W, ldw, out, 0, M, (int)(N / 256), K);
+  Operands o = operands(X, ldx, W, ldw, out, 0, M, 0, K, cossin);
+  o.Sq = S, o.Hq = Hq, o.Hkv = Hkv;
+  if (!takes(F_TN_ROPE, o)) return (int)hipErrorInvalidValue;
+  Args a = base_args(X, ldx, W, ldw, out, 0, M, (Hq + 2 * Hkv) / 2, K);
   a.S = (uint64_t)cossin;
   a.fw = (uint32_t)S;
   a.fc = (uint32_t)(Hq | (Hkv << 16));
@@ -716,8 +698,7 @@ extern "C" int toa_gemm_asm_rope(const bf16_t* X, int64_t ldx, const bf16_t* W, 
 extern "C" int toa_gemm_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc,
                                   const bf16_t* O, float* ndelta, int M, int N, int K, int S, int H,
                                   hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !al16(O) ||
-      ndelta == nullptr || ((uintptr_t)ndelta & 3) || H <= 0 || (int64_t)H * 128 != N || S <= 0 || S % 256 || M % S)
+  if (!takes(F_TN_DELTA, with_delta(operands(X, ldx, W, ldw, C, ldc, M, N, K, O), ndelta, S, H)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)O;
@@ -727,20 +708,14 @@ extern "C" int toa_gemm_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t* W,
   return launch(K_DELTA, a, stream);
 }
 
-// ---- NN form: C[M][N] = X[M][K] W[K][N], W as stored (row stride ldw >= N).
-// N (the columns of W and C) a multiple of 256, K (the reduction, W's rows) a
-// multiple of 64 and >= 128, any 0 < M < 2^28 (kernarg `m`), strides multiples
-// of 8 elements, 16-byte aligned bases: the TN entries' checks with ldw
-// measured against N.  The tile order is the TN kernels' rule (the output is
-// [tokens, in features], like the forward).
-static bool nn_ok(int M, int N, int K, int64_t ldx, int64_t ldw, const void* X, const void* W, bool m_tail) {
-  return M > 0 && (m_tail || M % 256 == 0) && (int64_t)M < (1 << 28) && N > 0 && N % 256 == 0 && K >= 128 &&
-         K % 64 == 0 && ld_ok(ldx, K) && ld_ok(ldw, N) && al16(X) && al16(W);
-}
+// ---- NN form: C[M][N] = X[M][K] W[K][N], W as stored (row stride ldw >= N):
+// the TN entries' checks with ldw measured against N, any M through kernarg
+// `m`.  The tile order is the TN kernels' rule (the output is [tokens, in
+// features], like the forward).
 
 extern "C" int toa_gemm_nn_asm(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc,
                                int M, int N, int K, hipStream_t stream) {
-  if (!nn_ok(M, N, K, ldx, ldw, X, W, true) || !ld_ok(ldc, N) || !al16(C)) return (int)hipErrorInvalidValue;
+  if (!takes(F_NN, operands(X, ldx, W, ldw, C, ldc, M, N, K))) return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   return launch(kNnBase + NN_PLAIN, a, stream);
 }
@@ -749,8 +724,7 @@ extern "C" int toa_gemm_nn_asm(const bf16_t* X, int64_t ldx, const bf16_t* W, in
 extern "C" int toa_gemm_nn_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16_t* Wd, int64_t ldw,
                                           const bf16_t* GU, int64_t ldgu, bf16_t* dGU, int64_t lddgu, int M, int F,
                                           int K, hipStream_t stream) {
-  if (!nn_ok(M, F, K, ldy, ldw, dY, Wd, true) || !ld_ok(ldgu, 2 * F) || !ld_ok(lddgu, 2 * F) || !al16(GU) ||
-      !al16(dGU))
+  if (!takes(F_NN_SWIGLU_BWD, operands(dY, ldy, Wd, ldw, dGU, lddgu, M, F, K, GU, ldgu)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(dY, ldy, Wd, ldw, dGU, lddgu, M, F / 256, K);
   a.S = (uint64_t)GU;
@@ -764,8 +738,7 @@ extern "C" int toa_gemm_nn_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const b
 extern "C" int toa_gemm_nn_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
                                      int64_t ldc, const bf16_t* O, float* ndelta, int M, int N, int K, int S, int H,
                                      hipStream_t stream) {
-  if (!nn_ok(M, N, K, ldx, ldw, X, W, false) || !ld_ok(ldc, N) || !al16(C) || !al16(O) || ndelta == nullptr ||
-      ((uintptr_t)ndelta & 3) || H <= 0 || (int64_t)H * 128 != N || S <= 0 || S % 256 || M % S)
+  if (!takes(F_NN_DELTA, with_delta(operands(X, ldx, W, ldw, C, ldc, M, N, K, O), ndelta, S, H)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)O;
@@ -778,8 +751,7 @@ extern "C" int toa_gemm_nn_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t*
 // C = X W^T + R, R bf16 laid out like C (gemm_gen.py epilogue_resadd).
 extern "C" int toa_gemm_asm_resadd(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C, int64_t ldc,
                                    const bf16_t* R, int M, int N, int K, hipStream_t stream) {
-  if (!common_ok(M, K, ldx, ldw, X, W, true) || N <= 0 || N % 256 || !ld_ok(ldc, N) || !al16(C) || !al16(R))
-    return (int)hipErrorInvalidValue;
+  if (!takes(F_TN_RESADD, operands(X, ldx, W, ldw, C, ldc, M, N, K, R))) return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)R;
   return launch(K_RESADD, a, stream);
@@ -791,8 +763,8 @@ extern "C" int toa_gemm_asm_resadd(const bf16_t* X, int64_t ldx, const bf16_t* W
 extern "C" int toa_gemm_asm_swiglu_bwd_variant(int v, const bf16_t* dY, int64_t ldy, const bf16_t* WdT, int64_t ldw,
                                                const bf16_t* GU, int64_t ldgu, bf16_t* dGU, int64_t lddgu, int M,
                                                int F, int K, hipStream_t stream) {
-  if (v < 0 || v > K_PLAIN_V9 - K_SWBWD_V1 || !common_ok(M, K, ldy, ldw, dY, WdT) || F <= 0 || F % 256 ||
-      !ld_ok(ldgu, 2 * F) || !ld_ok(lddgu, 2 * F) || !al16(GU) || !al16(dGU))
+  if (v < 0 || v > K_PLAIN_V9 - K_SWBWD_V1 || M % 256 ||   // (the arms: whole tiles only)
+      !takes(F_TN_SWIGLU_BWD, operands(dY, ldy, WdT, ldw, dGU, lddgu, M, F, K, GU, ldgu)))
     return (int)hipErrorInvalidValue;
   Args a = base_args(dY, ldy, WdT, ldw, dGU, lddgu, M, F / 256, K);
   a.S = (uint64_t)GU;

@@ -31,6 +31,7 @@
 
 #include <cstdint>
 
+#include "gemm_asm_shapes.h"
 #include "toa_common.h"
 
 #define WG_BM 256
@@ -295,26 +296,10 @@ __global__ __launch_bounds__(256) void wgrad_tile_reduce_kernel(const float* __r
   if (sq != nullptr) sq[((int64_t)tm * (N / WG_BN) + tn) * 256 + threadIdx.x] = ss;
 }
 
-static bool wg_split_ok(int K, int s) { return K % (4 * WG_BK * s) == 0 && K / s >= 16 * WG_BK; }
-
-// The launch plan: `full` whole-K tiles (whole waves of the 256 CUs, one
-// workgroup per CU: 128 KiB LDS) and the tail tiles cut into `split` pieces
-// so the last wave is as full as possible.  No tail: split 1.
-static void wg_plan(int M, int N, int K, int* full, int* split) {
-  const int tiles = (M / WG_BM) * (N / WG_BN);
-  const int rem = tiles % 256;
-  *full = tiles - rem;
-  *split = 1;
-  if (rem == 0) return;
-  int best = 1;
-  for (int s = 2; s <= 4; ++s)
-    if (rem * s <= 256 && wg_split_ok(K, s)) best = s;
-  if (best == 1) {  // nothing to split: the tail runs whole
-    *full = tiles;
-    return;
-  }
-  *split = best;
-}
+// The launch plan (whole-K tiles for whole waves of the 256 CUs, one
+// workgroup per CU: 128 KiB LDS; the tail tiles cut into k-pieces) and the
+// shapes this kernel takes: gemm_asm_shapes.h wgrad_plan / check_wgrad_hip.
+static_assert(WG_BM == 256 && WG_BN == 256 && 4 * WG_BK == 128, "gemm_asm_shapes.h states the plan in these tiles");
 
 // The reduce kernel of a split plan, for the assembly NT kernel
 // (csrc/hip/gemm_asm.hip toa_wgrad_asm), which writes the same tile-major
@@ -339,40 +324,28 @@ extern "C" int toa_wgrad_reduce(const float* W, bf16_t* C, int64_t ldc, int M, i
 }
 
 // Auto plan's split factor (1 = no split-K at all).
-extern "C" int toa_wgrad_split(int M, int N, int K) {
-  int full, split;
-  wg_plan(M, N, K, &full, &split);
-  return split;
-}
+extern "C" int toa_wgrad_split(int M, int N, int K) { return toa_shapes::wgrad_plan(M, N, K, 0, false).split; }
 
 // Bytes of fp32 workspace toa_wgrad needs: split == 0 = the auto plan, else
 // `split` K-pieces for every tile.
 extern "C" int64_t toa_wgrad_workspace(int M, int N, int K, int split) {
-  const int tiles = (M / WG_BM) * (N / WG_BN);
-  int full = 0;
-  if (split == 0) wg_plan(M, N, K, &full, &split);
-  else full = split == 1 ? tiles : 0;
-  return split > 1 ? (int64_t)split * (tiles - full) * WG_BM * WG_BN * 4 : 0;
+  return toa_shapes::wgrad_workspace(M, N, K, split, false);
 }
 
-// dW[M][N] (+)= dY[K][M]^T X[K][N].  M, N multiples of 256, K of 128 * split,
-// row strides multiples of 8 elements, 16-byte aligned bases.  split == 0:
+// dW[M][N] (+)= dY[K][M]^T X[K][N].  M, N multiples of 256, K of 128 * split
+// from 1024, row strides multiples of 8 elements, 16-byte aligned bases.  split == 0:
 // the auto plan (whole-K waves + a split tail); split >= 1: every tile cut
 // into `split` K-pieces (1 = none).
 extern "C" int toa_wgrad(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C, int64_t ldc,
                          float* W, int M, int N, int K, int split, int beta, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || M % WG_BM || N % WG_BN || split < 0 || (lda | ldb | ldc) % 8)
-    return (int)hipErrorInvalidValue;
-  const int tiles = (M / WG_BM) * (N / WG_BN);
-  int full;
-  if (split == 0) {
-    wg_plan(M, N, K, &full, &split);
-  } else {
-    full = split == 1 ? tiles : 0;
-  }
-  if (K % (4 * WG_BK * split) || (split > 1 && W == nullptr) || (split == 1 && full != tiles))
-    return (int)hipErrorInvalidValue;
-  const int rem = tiles - full;
+  toa_shapes::Operands o = {};
+  o.X = (uintptr_t)A, o.W = (uintptr_t)B, o.C = (uintptr_t)C, o.S = (uintptr_t)W;
+  o.ldx = lda, o.ldw = ldb, o.ldc = ldc;
+  o.M = M, o.N = N, o.K = K, o.split = split;
+  toa_shapes::WgradPlan plan;
+  if (toa_shapes::check_wgrad_hip(o, &plan) != toa_shapes::R_OK) return (int)hipErrorInvalidValue;
+  split = plan.split;
+  const int full = plan.full, rem = (M / WG_BM) * (N / WG_BN) - full;
   const int nwg = full + (split > 1 ? rem * split : 0);
   hipLaunchKernelGGL(wgrad_nt_kernel, dim3(nwg), dim3(512), 0, stream, A, lda, B, ldb, C, ldc, W, M, N, K, full, split,
                      beta);

@@ -155,6 +155,8 @@ _SIGS = {
     "toa_gemm_tune": [c_int, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_f, c_int, c_p, c_p, c_p,
                       c_p, c_p, c_int],
     "toa_gemm_kernel_name": [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_p, c_int],
+    # form, X W C S D, ldx ldw ldc lds, M N K, S H Hq Hkv split (csrc/hip/gemm_asm_shapes.h Operands)
+    "toa_gemm_shape_check": [c_int] + [c_p] * 5 + [c_i64] * 4 + [c_int] * 8,
 }
 
 
@@ -192,6 +194,9 @@ def _load():
         wa = getattr(lib, "toa_wgrad_asm_workspace", None)
         if wa is not None:
             wa.argtypes, wa.restype = [c_int, c_int, c_int, c_int], c_i64
+        sw = getattr(lib, "toa_gemm_shape_why", None)
+        if sw is not None:
+            sw.argtypes, sw.restype = [c_int], ctypes.c_char_p
         _lib = lib
 
 
@@ -218,7 +223,7 @@ def has(name: str) -> bool:
 
 # launchers whose argument / result types _load sets outside _SIGS
 _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coherent_alloc", "toa_wgrad_workspace",
-                    "toa_wgrad_asm_workspace"}
+                    "toa_wgrad_asm_workspace", "toa_gemm_shape_why"}
 
 
 def _fn(name: str):
@@ -241,6 +246,27 @@ def call(name: str, *args):
 def call_ret(name: str, *args) -> int:
     """Invoke `name` and return its int result (no error check)."""
     return _fn(name)(*args)
+
+
+# the product forms of csrc/hip/gemm_asm_shapes.h, in its enum Form's order
+SHAPE_FORMS = ("tn", "tn_rows", "tn_swiglu_fwd", "tn_swiglu_bwd", "tn_rope", "tn_delta", "tn_resadd", "nn",
+               "nn_swiglu_bwd", "nn_delta", "wgrad_asm", "wgrad_hip")
+_FORM_ID = {name: i for i, name in enumerate(SHAPE_FORMS)}
+
+
+def shape_check(form: str, tensors, lds, M, N, K, S=0, H=0, Hq=0, Hkv=0, split=0) -> int:
+    """What the launcher of `form` says to these operands, asked on the host
+    (toa_gemm_shape_check): 0 = taken, else the reason :func:`shape_why`
+    names.  tensors: X, W, then C, S, D of that form's Operands slots (None =
+    not allocated yet, short = the rest None); lds: their row strides in
+    elements (ldx, ldw, ldc, lds)."""
+    ptrs = [0 if t is None else t.data_ptr() for t in tensors]
+    return lib().toa_gemm_shape_check(_FORM_ID[form], *ptrs, *(0,) * (5 - len(ptrs)), *lds, *(0,) * (4 - len(lds)),
+                                      M, N, K, S, H, Hq, Hkv, split)
+
+
+def shape_why(reason: int) -> str:
+    return _fn("toa_gemm_shape_why")(reason).decode()
 
 
 def stream(t: torch.Tensor | None = None):

@@ -236,20 +236,10 @@ def reset_fallbacks():
         _FALLBACKS.clear()
 
 
-def _why_not_asm(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> str:
-    M, K = x2.shape
-    N = w.shape[0]
-    if x2.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
-        return f"dtype {x2.dtype}/{w.dtype}, not bf16"
-    if not 0 < M < 1 << 28:
-        return f"M={M} (tokens per micro-batch x seq) outside 1 .. 2^28 - 1"
-    if M % 256 and _MODE != "asm":
-        return f"M={M} not a multiple of 256 outside the asm policy (first_step takes whole tiles only)"
-    if N % n_mult:
-        return f"N={N} (output features) not a multiple of {n_mult}; only the token count M is free"
-    if K % 64 or K < 128:
-        return f"K={K} not a multiple of 64 >= 128"
-    return "layout: non-unit column stride, unaligned rows or base"
+def _refused(reason: int, M, N, K) -> str:
+    """The fallback warning's reason: the launcher's own words for the first
+    condition that failed (toa_gemm_shape_why), with the shape."""
+    return f"{_lib.shape_why(reason)}: M={M} N={N} K={K}"
 
 
 class first_step:
@@ -278,30 +268,50 @@ class first_step:
         return False
 
 
-def asm_takes(x2: torch.Tensor, w: torch.Tensor, n_mult: int = 256) -> bool:
-    """Operands the assembly GEMM takes: the host-side checks of
-    csrc/hip/gemm_asm.hip (``common_ok`` / ``ld_ok`` / ``al16``, which refuse
-    anything else) on x2 [M, K] and w [N, K].  bf16 GPU rows with unit column
-    stride, 16-byte aligned bases, row strides >= K, multiples of 8 and under
-    2^23 elements, any 0 < M < 2^28 (the token count: the last tile row's
-    tail is cut by the kernels' buffer resources, docs/kernels.md; under
-    first_step, a hipBLASLt policy's start-up, multiples of 256 only as
-    before), N a multiple of 256 (n_mult), K a multiple of 64 and >= 128.  The fused
-    epilogues' predicates (ops/llm.py) build on it and add only what their
-    own launcher checks -- the RoPE and delta epilogues their S % 256 == 0."""
-    if not (_MODE == "asm" or _asm_first) or not _lib.has("toa_gemm_asm"):
-        return False
-    if not (x2.is_cuda and x2.dtype == w.dtype == torch.bfloat16 and x2.dim() == 2 and w.dim() == 2):
-        return False
-    M, K = x2.shape
+def _kind_why(*ts) -> str:
+    """What the launchers' checks cannot see -- bf16 GPU matrices with unit
+    column stride: the first tensor property that is not so, "" if all are."""
+    for t in ts:
+        if not (t.is_cuda and t.dim() == 2):
+            return f"a {t.dim()}-D {t.device.type} tensor, not a GPU matrix"
+        if t.dtype != torch.bfloat16:
+            return f"dtype {t.dtype}, not bf16"
+        if t.stride(1) != 1:
+            return f"column stride {t.stride(1)}, not 1"
+    return ""
+
+
+def _gate_why(a: torch.Tensor, w: torch.Tensor, wk: int, kernel: str) -> str:
+    """Why (a [M, K], w with K along dim wk) are no operands of `kernel`
+    before any shape is asked about, "" if they are."""
+    if not _lib.has(kernel):
+        return f"library built without {kernel}"
+    kind = _kind_why(a, w)
+    if not kind and w.shape[wk] != a.shape[1]:
+        kind = f"K={a.shape[1]} columns against {w.shape[wk]} in the weight"
+    return kind
+
+
+def _asm_gate(x2: torch.Tensor, w: torch.Tensor) -> bool:
+    """The policy runs the TN assembly GEMMs and (x2 [M, K], w [N, K]) are operands of one."""
+    return (_MODE == "asm" or _asm_first) and not _gate_why(x2, w, 1, "toa_gemm_asm") and _lib.use_hip(x2)
+
+
+def _tn_reason(x2: torch.Tensor, w: torch.Tensor) -> int:
+    """toa_gemm_shape_check for y [M, N] = x2 w^T, y contiguous.  The form is
+    the policy's choice: any row count under ``asm``, whole tiles only under
+    first_step (a hipBLASLt policy's start-up), as before."""
+    form = "tn_rows" if _MODE == "asm" and _lib.has("toa_gemm_asm_rows") else "tn"
     N = w.shape[0]
-    for t in (x2, w):
-        if t.stride(1) != 1 or t.stride(0) < K or t.stride(0) % 8 or t.stride(0) >= 1 << 23 or t.data_ptr() % 16:
-            return False
-    if M % 256 and not (_MODE == "asm" and _lib.has("toa_gemm_asm_rows")):
-        return False
-    return (0 < M < 1 << 28 and N > 0 and N % n_mult == 0 and K % 64 == 0 and K >= 128
-            and w.shape[1] == K and _lib.use_hip(x2))
+    return _lib.shape_check(form, (x2, w), (x2.stride(0), w.stride(0), N), x2.shape[0], N, x2.shape[1])
+
+
+def asm_takes(x2: torch.Tensor, w: torch.Tensor) -> bool:
+    """Operands the assembly GEMM takes for x2 [M, K] w [N, K]^T: bf16 GPU
+    rows with unit column stride under a policy that runs it, and a shape its
+    launcher takes (csrc/hip/gemm_asm_shapes.h; the table in docs/kernels.md).
+    The fused epilogues' predicates (ops/llm.py) ask about their own forms."""
+    return _asm_gate(x2, w) and _tn_reason(x2, w) == 0
 
 
 def linear_fwd(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -315,8 +325,9 @@ def linear_fwd(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         return y
     lib_ok = _ok(x2, w)
     if _MODE == "asm" and x2.is_cuda and x2.dim() == 2 and w.dim() == 2:
-        _fallback("fwd", (x2.shape[0], w.shape[0], x2.shape[1]), "hipBLASLt" if lib_ok else "torch.matmul",
-                  _why_not_asm(x2, w))
+        M, N, K = x2.shape[0], w.shape[0], x2.shape[1]
+        _fallback("fwd", (M, N, K), "hipBLASLt" if lib_ok else "torch.matmul",
+                  _gate_why(x2, w, 1, "toa_gemm_asm") or _refused(_tn_reason(x2, w), M, N, K))
     if not lib_ok:
         return torch.matmul(x2, w.t())
     M, K = x2.shape
@@ -363,36 +374,20 @@ def set_dgrad_form(name: str):
     _DGRAD_FORM = name
 
 
-def _why_not_nn(dy2: torch.Tensor, w: torch.Tensor) -> str:
-    """The first check of toa_gemm_nn_asm that (dy2 [M, K], w [K, N]) fails, "" if none."""
-    if not _lib.has("toa_gemm_nn_asm"):
-        return "library built without toa_gemm_nn_asm"
-    if not (dy2.is_cuda and dy2.dim() == 2 and w.dim() == 2):
-        return "not 2-D GPU tensors"
-    if dy2.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
-        return f"dtype {dy2.dtype}/{w.dtype}, not bf16"
-    M, K = dy2.shape
+def _nn_gate(dy2: torch.Tensor, w: torch.Tensor) -> bool:
+    """The policy runs the NN assembly GEMMs and (dy2 [M, K], w [K, N] as stored) are operands of one."""
+    return _MODE == "asm" and not _gate_why(dy2, w, 0, "toa_gemm_nn_asm") and _lib.use_hip(dy2)
+
+
+def _nn_reason(dy2: torch.Tensor, w: torch.Tensor) -> int:
     N = w.shape[1]
-    if w.shape[0] != K:
-        return f"dY has {K} columns, W {w.shape[0]} rows"
-    if not 0 < M < 1 << 28:
-        return f"M={M} (tokens) outside 1 .. 2^28 - 1"
-    if N <= 0 or N % 256:
-        return f"N={N} (in features) not a multiple of 256"
-    if K % 64 or K < 128:
-        return f"K={K} (out features) not a multiple of 64 >= 128"
-    for t, cols in ((dy2, K), (w, N)):
-        if t.stride(1) != 1 or t.stride(0) < cols or t.stride(0) % 8 or t.stride(0) >= 1 << 23 or t.data_ptr() % 16:
-            return "layout: non-unit column stride, unaligned rows or base"
-    return ""
+    return _lib.shape_check("nn", (dy2, w), (dy2.stride(0), w.stride(0), N), dy2.shape[0], N, dy2.shape[1])
 
 
 def nn_takes(dy2: torch.Tensor, w: torch.Tensor) -> bool:
-    """Operands the NN-form assembly GEMM takes for dX = dy2 w: the host-side
-    checks of csrc/hip/gemm_asm.hip's toa_gemm_nn_asm (``nn_ok`` / ``ld_ok`` /
-    ``al16``) on dy2 [M, K] and w [K, N] as stored, under the ``asm`` policy:
-    any 0 < M < 2^28, N a multiple of 256, K a multiple of 64 and >= 128."""
-    return _MODE == "asm" and not _why_not_nn(dy2, w) and _lib.use_hip(dy2)
+    """Operands the NN-form assembly GEMM takes for dX = dy2 [M, K] w [K, N]
+    (w as stored) under the ``asm`` policy: see asm_takes."""
+    return _nn_gate(dy2, w) and _nn_reason(dy2, w) == 0
 
 
 def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -408,7 +403,8 @@ def linear_dgrad(dy2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
             _lib.call("toa_gemm_nn_asm", _lib.ptr(dy2), dy2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(dx), N,
                       M, N, dy2.shape[1], _lib.stream(dy2))
             return dx
-        why = f"NN form refused: {_why_not_nn(dy2, w) or 'not on the HIP device'}"
+        why = "NN form refused: " + (_gate_why(dy2, w, 0, "toa_gemm_nn_asm")
+                                     or _refused(_nn_reason(dy2, w), dy2.shape[0], w.shape[1], dy2.shape[1]))
     lib_ok = _ok(dy2, w)
     if _MODE == "asm" and dy2.is_cuda and dy2.dim() == 2 and w.dim() == 2:
         _fallback("dgrad", (dy2.shape[0], w.shape[1], dy2.shape[1]), "hipBLASLt" if lib_ok else "torch.matmul", why)
@@ -425,9 +421,10 @@ def swiglu_gate_up(x2: torch.Tensor, wgu: torch.Tensor):
     """(gu, s) = (x Wgu^T, silu(gate) * up) from ONE assembly GEMM with the
     SwiGLU in its epilogue; None when the kernel cannot take the shapes."""
     reading(wgu, "swiglu_gate_up")
-    if not (asm_takes(x2, wgu, n_mult=2) and (wgu.shape[0] // 2) % 128 == 0):
+    M, F, K = x2.shape[0], wgu.shape[0] // 2, x2.shape[1]
+    if not (_asm_gate(x2, wgu) and wgu.shape[0] == 2 * F and _lib.shape_check(
+            "tn_swiglu_fwd", (x2, wgu), (x2.stride(0), wgu.stride(0), 2 * F, F), M, F, K) == 0):
         return None
-    M, F = x2.shape[0], wgu.shape[0] // 2
     gu = torch.empty(M, 2 * F, device=x2.device, dtype=x2.dtype)
     s = torch.empty(M, F, device=x2.device, dtype=x2.dtype)
     _lib.call("toa_gemm_asm_swiglu", _lib.ptr(x2), x2.stride(0), _lib.ptr(wgu), wgu.stride(0), _lib.ptr(gu), 2 * F,
@@ -443,18 +440,23 @@ def swiglu_down_dgrad(d2: torch.Tensor, wd: torch.Tensor, gu: torch.Tensor):
     reading(wd, "swiglu_down_dgrad")
     wdt = getattr(wd, "_toa_wt", None)
     if wdt is None and dgrad_form() == "nn":     # on Wd [D, F] as stored (the NN form)
-        if not (nn_takes(d2, wd) and _lib.has("toa_gemm_nn_asm_swiglu_bwd") and gu.is_contiguous()
-                and gu.shape[1] == 2 * wd.shape[1] and gu.data_ptr() % 16 == 0):
-            return None
         M, F = d2.shape[0], wd.shape[1]
+        if not (_nn_gate(d2, wd) and _lib.has("toa_gemm_nn_asm_swiglu_bwd") and gu.is_contiguous()
+                and gu.shape[1] == 2 * F and _lib.shape_check(
+                    "nn_swiglu_bwd", (d2, wd, None, gu), (d2.stride(0), wd.stride(0), 2 * F, 2 * F), M, F,
+                    d2.shape[1]) == 0):
+            return None
         dgu = torch.empty_like(gu)
         _lib.call("toa_gemm_nn_asm_swiglu_bwd", _lib.ptr(d2), d2.stride(0), _lib.ptr(wd), wd.stride(0), _lib.ptr(gu),
                   2 * F, _lib.ptr(dgu), 2 * F, M, F, d2.shape[1], _lib.stream(d2))
         return dgu
-    if wdt is None or not (asm_takes(d2, wdt) and gu.is_contiguous() and gu.shape[1] == 2 * wdt.shape[0]
-                           and gu.data_ptr() % 16 == 0):
+    if wdt is None:
         return None
     M, F = d2.shape[0], wdt.shape[0]
+    if not (_asm_gate(d2, wdt) and gu.is_contiguous() and gu.shape[1] == 2 * F and _lib.shape_check(
+            "tn_swiglu_bwd", (d2, wdt, None, gu), (d2.stride(0), wdt.stride(0), 2 * F, 2 * F), M, F,
+            d2.shape[1]) == 0):
+        return None
     dgu = torch.empty_like(gu)
     _lib.call("toa_gemm_asm_swiglu_bwd", _lib.ptr(d2), d2.stride(0), _lib.ptr(wdt), wdt.stride(0), _lib.ptr(gu),
               2 * F, _lib.ptr(dgu), 2 * F, M, F, d2.shape[1], _lib.stream(d2))
@@ -504,36 +506,44 @@ def _workspace(dev, nbytes):
     return t
 
 
-def _hip_wgrad_takes_tokens(T: int) -> bool:
-    """Token counts csrc/hip/wgrad.hip takes (its plan and its k-loop)."""
-    return T % 128 == 0 and T >= 1024
+def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:
+    """toa_gemm_shape_check for g [N, K] (+)= dy2 [T, N]^T x2 [T, K] on the
+    assembly ("wgrad_asm") or the HIP ("wgrad_hip") kernel.  g stands in for
+    the split-K workspace, which is allocated per call (_workspace), aligned."""
+    T, N = dy2.shape
+    K = x2.shape[1]
+    return _lib.shape_check(form, (dy2, x2, g, g), (dy2.stride(0), x2.stride(0), K), N, K, T, split=split)
 
 
-def _asm_wgrad_takes_tokens(T: int) -> bool:
-    """Token counts the assembly kernel takes when it is the selected one
-    (csrc/hip/gemm_asm.hip wgrad_asm_launch): any T >= 65 -- ceil(T / 64) >= 2
-    k-tiles, the last one's rows past T read as 0 through the operands'
-    buffer resources."""
-    return wgrad_kernel() in ("asm", "asm_v1") and _lib.has("toa_wgrad_asm_workspace") and T >= 65
+def _wgrad_asm_selected() -> bool:
+    return wgrad_kernel() in ("asm", "asm_v1") and _lib.has("toa_wgrad_asm_workspace")
+
+
+def _wgrad_gate_why(g, dy2, x2) -> str:
+    """Why (g, dy2 [T, N], x2 [T, K]) are no operands of the hand-written
+    weight-gradient kernels before any shape is asked about, "" if they are."""
+    if not _lib.has("toa_wgrad"):
+        return "library built without toa_wgrad"
+    kind = _kind_why(dy2, x2)
+    if kind:
+        return kind
+    if g.dtype != torch.bfloat16:
+        return f"gradient dtype {g.dtype}, not bf16"
+    if x2.shape[0] != dy2.shape[0]:
+        return f"T={dy2.shape[0]} rows of dy against {x2.shape[0]} of x"
+    if not g.is_contiguous() or tuple(g.shape) != (dy2.shape[1], x2.shape[1]):
+        return f"gradient {tuple(g.shape)} with strides {g.stride()}, not a contiguous [N, K]"
+    return ""
 
 
 def wgrad_hip_ok(g, dy2, x2) -> bool:
-    """Shapes/layouts the hand-written weight-gradient kernels take: bf16,
-    256-multiple output dims, unit column stride, and a token count either
-    kernel takes -- csrc/hip/wgrad.hip multiples of 128 from 1024, the
-    assembly kernel (when selected) any T >= 65."""
-    if not _lib.has("toa_wgrad"):
-        return False
-    if not (dy2.is_cuda and g.dtype == dy2.dtype == x2.dtype == torch.bfloat16 and g.is_contiguous()):
-        return False
-    if dy2.dim() != 2 or x2.dim() != 2 or dy2.stride(1) != 1 or x2.stride(1) != 1:
-        return False
-    T, N = dy2.shape
-    K = x2.shape[1]
-    tokens_ok = _hip_wgrad_takes_tokens(T) or _asm_wgrad_takes_tokens(T)
-    return (N % 256 == 0 and K % 256 == 0 and tokens_ok and dy2.stride(0) % 8 == 0
-            and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0
-            and g.data_ptr() % 16 == 0 and tuple(g.shape) == (N, K))
+    """Shapes/layouts the hand-written weight-gradient kernels take: bf16
+    rows with unit column stride, a contiguous g [N, K], and a shape the
+    assembly kernel (when selected) or csrc/hip/wgrad.hip takes
+    (csrc/hip/gemm_asm_shapes.h)."""
+    return not _wgrad_gate_why(g, dy2, x2) and (
+        (_wgrad_asm_selected() and _wgrad_reason("wgrad_asm", g, dy2, x2) == 0)
+        or _wgrad_reason("wgrad_hip", g, dy2, x2) == 0)
 
 
 class SumsqSession:
@@ -638,9 +648,10 @@ def wgrad_hip_(g, dy2, x2, beta=1.0, split=None):
     T, N = dy2.shape
     K = x2.shape[1]
     split = 0 if split is None else int(split)
-    # a token count only the assembly kernel takes: its own plan (the split
-    # divides the ceil(T / 64) k-tiles), and never the HIP kernel below
-    hip_takes = _hip_wgrad_takes_tokens(T)
+    # operands only the assembly kernel takes (a token count or a forced
+    # split that csrc/hip/wgrad.hip refuses): its own plan (the split divides
+    # the ceil(T / 64) k-tiles), and never the HIP kernel below
+    hip_takes = _wgrad_reason("wgrad_hip", g, dy2, x2, split) == 0
     nbytes = int(_lib.call_ret("toa_wgrad_workspace" if hip_takes else "toa_wgrad_asm_workspace", N, K, T, split))
     ws = _workspace(dy2.device, nbytes) if nbytes > 0 else None
     args = (_lib.ptr(dy2), dy2.stride(0), _lib.ptr(x2), x2.stride(0), _lib.ptr(g), K, _lib.ptr(ws),
@@ -667,8 +678,8 @@ def wgrad_hip_(g, dy2, x2, beta=1.0, split=None):
         # a shape / layout the assembly kernel's launcher refuses (it checks
         # before launching): the HIP kernel shares its split plan and reduce
     if not hip_takes:
-        raise RuntimeError(f"weight gradient {N}x{K}x{T}: T={T} is a token count only the assembly kernel takes "
-                           f"(csrc/hip/wgrad.hip: T % 128 == 0, T >= 1024) and it "
+        raise RuntimeError(f"weight gradient {N}x{K}x{T}: csrc/hip/wgrad.hip does not take it ("
+                           + _lib.shape_why(_wgrad_reason("wgrad_hip", g, dy2, x2, split)) + ") and the assembly kernel "
                            + ("refused the operands" if kern in ("asm", "asm_v1") else f"is not selected ({kern})"))
     _lib.call("toa_wgrad", *args)
     return g
@@ -680,10 +691,11 @@ def wgrad_acc_(g: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor, beta: float
         return wgrad_hip_(g, dy2, x2, beta)
     if dy2.is_cuda and g.dtype == torch.bfloat16 and dy2.dim() == 2 and x2.dim() == 2:
         T, N = dy2.shape
-        _fallback("wgrad", (N, x2.shape[1], T), "hipBLASLt" if _ok(dy2, x2) else "torch.mm",
-                  "output dims not multiples of 256, layout, or tokens: "
-                  + ("under 65" if wgrad_kernel() in ("asm", "asm_v1")
-                     else "not a multiple of 128 (>= 1024) for the HIP kernel (TOA_WGRAD=hip)"))
+        why = f"beta={beta}, not 0 or 1" if beta not in (0.0, 1.0) else _wgrad_gate_why(g, dy2, x2)
+        if not why:
+            form = "wgrad_asm" if _wgrad_asm_selected() else "wgrad_hip"
+            why = form + ": " + _refused(_wgrad_reason(form, g, dy2, x2), N, x2.shape[1], T)
+        _fallback("wgrad", (N, x2.shape[1], T), "hipBLASLt" if _ok(dy2, x2) else "torch.mm", why)
     if (g.dtype == torch.float32 and dy2.dtype == x2.dtype == torch.bfloat16 and g.is_cuda and g.is_contiguous()
             and dy2.stride(1) == 1 and x2.stride(1) == 1 and _lib.has("toa_gemm")):
         # fp32 master-gradient accumulation (small payloads): one hipBLASLt call

@@ -231,9 +231,11 @@ def _resadd_ok(a2, w, residual, M) -> bool:
     """gemm.linear_resadd takes out [M, N] = a w^T + residual: operands the
     assembly GEMM takes (a2 has a's row layout) and a bf16, contiguous,
     16-byte aligned residual of the output's size."""
-    return (gemm.mode() == "asm" and gemm.asm_takes(a2, w) and 0 < M < 1 << 28
-            and residual.dtype == torch.bfloat16 and residual.is_contiguous() and residual.data_ptr() % 16 == 0
-            and residual.numel() == M * w.shape[0] and _lib.has("toa_gemm_asm_resadd") and resadd_fused_enabled())
+    N, K = w.shape[0], a2.shape[1]
+    return (gemm.mode() == "asm" and _lib.has("toa_gemm_asm_resadd") and resadd_fused_enabled()
+            and gemm._asm_gate(a2, w) and residual.dtype == torch.bfloat16 and residual.is_contiguous()
+            and residual.numel() == M * N
+            and _lib.shape_check("tn_resadd", (a2, w, None, residual), (a2.stride(0), w.stride(0), N), M, N, K) == 0)
 
 
 def swiglu_mlp_resadd_ok(x, wd, residual) -> bool:
@@ -473,15 +475,13 @@ class _AttnOutProj(torch.autograd.Function):
             T, N = o2.shape
             dx = torch.empty_like(o2)
             nd = torch.empty(B * H * S, device=o2.device, dtype=torch.float32)
-            rc = _lib.call_ret(fn, _lib.ptr(dy2), dy2.stride(0), _lib.ptr(wmat), wmat.stride(0),
-                               _lib.ptr(dx), dx.stride(0), _lib.ptr(o2), _lib.ptr(nd), T, N, dy2.shape[1], S, H,
-                               _lib.stream(dy2))
-            if rc == 0:
+            if _lib.shape_check("tn_delta" if wt is not None else "nn_delta", (dy2, wmat, dx, o2, nd),
+                                (dy2.stride(0), wmat.stride(0), dx.stride(0)), T, N, dy2.shape[1], S=S, H=H) == 0:
+                _lib.call(fn, _lib.ptr(dy2), dy2.stride(0), _lib.ptr(wmat), wmat.stride(0), _lib.ptr(dx),
+                          dx.stride(0), _lib.ptr(o2), _lib.ptr(nd), T, N, dy2.shape[1], S, H, _lib.stream(dy2))
                 ctx.link.put(dx, nd)
-            elif rc == 1:   # hipErrorInvalidValue: a shape it does not take
+            else:   # a shape the delta epilogue does not take
                 dx = None
-            else:
-                raise RuntimeError(f"{fn} failed with hipError {rc}")
         if dx is None and ctx.needs_input_grad[0]:
             dx = gemm.linear_dgrad(dy2, wo)
         dw = accumulate_mm(wo, dy2.t(), o2)
@@ -551,16 +551,15 @@ class _QKVRopeAttn(torch.autograd.Function):
 
 
 def qkv_rope_attention_ok(x, wqkv, S, Hq, Hkv, D) -> bool:
-    """The fused projection + RoPE path applies: the assembly policy,
-    operands the assembly GEMM takes (N = (Hq + 2 Hkv) 128 a multiple of 256
-    among them) and what toa_gemm_asm_rope checks on top -- head dim 128, S a
-    multiple of 256 dividing M, its head-count and 32-bit offset limits."""
+    """The fused projection + RoPE path applies: the assembly policy, head
+    dim 128 with grouped query heads, a weight of (Hq + 2 Hkv) 128 rows, and
+    operands toa_gemm_asm_rope takes (the "tn_rope" form)."""
     x2 = x.reshape(-1, x.shape[-1])
-    M, N = x2.shape[0], wqkv.shape[0]
-    return (gemm.mode() == "asm" and gemm.asm_takes(x2, wqkv) and D == 128 and N == (Hq + 2 * Hkv) * D
-            and S > 0 and S % 256 == 0 and M % S == 0 and 0 < Hkv <= Hq <= 4096 and Hq % Hkv == 0
-            and M * N * 2 < 2 ** 32 and S * 512 + 128 * 256 < 2 ** 32
-            and os.environ.get("TOA_QKV_ROPE", "1") != "0" and _lib.has("toa_gemm_asm_rope"))
+    return (gemm.mode() == "asm" and os.environ.get("TOA_QKV_ROPE", "1") != "0" and _lib.has("toa_gemm_asm_rope")
+            and gemm._asm_gate(x2, wqkv) and D == 128 and wqkv.shape[0] == (Hq + 2 * Hkv) * D
+            and _lib.shape_check("tn_rope", (x2, wqkv), (x2.stride(0), wqkv.stride(0)), x2.shape[0], 0, x2.shape[1],
+                                 S=S, Hq=Hq, Hkv=Hkv) == 0
+            and Hq % Hkv == 0)
 
 
 def qkv_rope_attention(x, wqkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd", cossin=None, link=None):

@@ -218,11 +218,27 @@ __device__ __forceinline__ void fwd_block_coords(int pid, int nqb, int B, int H,
   }
 }
 
-template <int D, bool TAIL>
+// Document mask (the DOC template arms; toa_attn_fwd_doc / toa_attn_bwd_doc):
+// query i sees key j iff doc_start[i] <= j <= i, which for j <= i is
+// i < doc_end[j].  The arrays only feed compares and loop bounds and are
+// clamped where they are read -- doc_start[i] into [0, i], doc_end[j] into
+// [j + 1, S], the index into [0, S - 1] -- so a wrong array gives wrong
+// numbers, never an out-of-range tile.
+__device__ __forceinline__ int doc_row_start(const int* __restrict__ ds, int i, int S) {
+  const int ic = min(i, S - 1);
+  return min(max(ds[ic], 0), ic);
+}
+__device__ __forceinline__ int doc_key_end(const int* __restrict__ de, int j, int S) {
+  const int jc = min(j, S - 1);
+  return min(max(de[jc], jc + 1), S);
+}
+
+template <int D, bool TAIL, bool DOC = false>
 __global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
                                                           float* __restrict__ LSE, int B, int H, int Hk, int S,
-                                                          float scale_log2, int o_bshd) {
+                                                          float scale_log2, int o_bshd,
+                                                          const int* __restrict__ DSTART = nullptr) {
   using G = AG<D>;
   constexpr int ROWB = G::ROWB, NCH = G::NCH, NS = G::NS, ND = G::ND, TILEB = G::TILEB;
   constexpr int NL = TK * NCH / 512;  // 16-B chunks of K (and of V) per thread per tile
@@ -242,6 +258,16 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const bf16_t* __restri
   const int kend = min(S, (qb + 1) * FWD_QB);
   const int ntiles = (kend + TK - 1) / TK;
   const int t_diag = live ? (q0 + 31) / TK : -1;  // this wave's last (masked) tile
+  // document mask (see doc_row_start): the block's first tile, the wave's
+  // first tile, the wave's largest start and the lane's own row's start
+  int t_beg = 0, t_lo = 0, ds_hi = 0, ds_my = 0;
+  if constexpr (DOC) {
+    const int* dsb = DSTART + (int64_t)b * S;
+    t_beg = doc_row_start(dsb, qb * FWD_QB, S) / TK;
+    t_lo = __builtin_amdgcn_readfirstlane(doc_row_start(dsb, q0, S)) / TK;
+    ds_hi = __builtin_amdgcn_readfirstlane(doc_row_start(dsb, q0 + 31, S));
+    ds_my = doc_row_start(dsb, myq, S);
+  }
 
   // Q fragments: Q[myq][16s + 8hh .. +7], s = 0..NS-1
   bf16x8 qf[NS];
@@ -312,7 +338,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const bf16_t* __restri
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
           const int key = t * TK + 32 * n + (j & 3) + 8 * (j >> 2) + 4 * hh;
-          if (key > myq) sc[n][j] = -INFINITY;
+          if (key > myq || (DOC && key < ds_my)) sc[n][j] = -INFINITY;
         }
     }
     float mx = rowmax32(sc[0], sc[1]);
@@ -330,7 +356,11 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const bf16_t* __restri
     }
     // ---- P = exp2(s*c - m) packed straight into the PV B operand
     f32x2 ls;
-    const f32x2 c2 = {scale_log2, scale_log2}, nm2 = {-m_run, -m_run};
+    // DOC: a row whose every key so far was another document's still has
+    // m_run = -inf, and -inf * c + inf is NaN: subtract 0 instead, so each
+    // of its p is exp2(-inf) = 0 and the row adds nothing to l or O
+    const float m_sub = (DOC && m_run == -INFINITY) ? 0.f : m_run;
+    const f32x2 c2 = {scale_log2, scale_log2}, nm2 = {-m_sub, -m_sub};
     uint32_t pw[2][8];
 #pragma unroll
     for (int n = 0; n < 2; ++n)
@@ -366,13 +396,20 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const bf16_t* __restri
   };
   auto step = [&](int t, int buf) {
     if (t + 1 < ntiles) gload(t + 1);
-    if (t < t_diag) compute(t, buf, false);
-    else if (t == t_diag) compute(t, buf, true);
+    if constexpr (DOC) {
+      // tiles before the wave's first document hold no visible key: not
+      // computed at all; a tile with keys below some row's start is masked
+      if (t >= t_lo && t < t_diag && t * TK >= ds_hi) compute(t, buf, false);
+      else if (t >= t_lo && t <= t_diag) compute(t, buf, true);
+    } else {
+      if (t < t_diag) compute(t, buf, false);
+      else if (t == t_diag) compute(t, buf, true);
+    }
     if (t + 1 < ntiles) swrite(buf ^ 1);
     __syncthreads();
   };
 
-  gload(0);
+  gload(t_beg);
   swrite(0);
   // Retire the Q loads HERE.  Left to itself the compiler sinks them past the
   // barrier; the loop then inherits "Q pending" and, vmcnt being in-order,
@@ -380,7 +417,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_kernel(const bf16_t* __restri
 #pragma unroll
   for (int s = 0; s < NS; ++s) asm volatile("" ::"v"(qf[s]));
   __syncthreads();
-  int t = 0;
+  int t = t_beg;
   for (; t + 1 < ntiles; t += 2) {  // unrolled by 2: buffer offsets become immediates
     step(t, 0);
     step(t + 1, 1);
@@ -641,12 +678,12 @@ struct DKV {
   static constexpr int LDS = 2 * QBUF + 2 * KVB;
 };
 
-template <int D, bool TAIL>
+template <int D, bool TAIL, bool DOC = false>
 __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ DELTA,
     bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, int B, int H, int Hk, int S, float scale,
-    float scale_log2, int o_bshd) {
+    float scale_log2, int o_bshd, const int* __restrict__ DEND = nullptr) {
   using G = AG<D>;
   constexpr int ROWB = G::ROWB, NCH = G::NCH, NS = G::NS, ND = G::ND, TILEB = G::TILEB;
   constexpr int QBUF = DKV<D>::QBUF, KVB = DKV<D>::KVB;
@@ -699,7 +736,18 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_kernel(
   }
 
   const int qt0 = (kb * 128) / 64;  // first causal 64-row query tile
-  const int nqt = (S + TK - 1) / TK - qt0;
+  // document mask (see doc_key_end): the key on the lane is seen by queries
+  // mykey .. de_my - 1; the sweep ends with the block's last key's document,
+  // a wave computes sub-tiles below de_hi and masks from de_lo on
+  int q_end = S, de_lo = 0, de_hi = 0, de_my = 0;
+  if constexpr (DOC) {
+    const int* deb = DEND + (int64_t)b * S;
+    q_end = doc_key_end(deb, kb * 128 + 127, S);
+    de_lo = __builtin_amdgcn_readfirstlane(doc_key_end(deb, kw, S));
+    de_hi = __builtin_amdgcn_readfirstlane(doc_key_end(deb, kw + 31, S));
+    de_my = doc_key_end(deb, mykey, S);
+  }
+  const int nqt = (q_end + TK - 1) / TK - qt0;
   const int total = nqt * rep;
   u32x4 sq[NLQ], sdo[NLQ];
   float slse = 0.f, sdel = 0.f;
@@ -772,8 +820,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_kernel(
       float p1 = EXP2(fmaf(sc[j + 1], scale_log2, l4[(j + 1) & 3]));
       if (mask) {
         const int q = qs + (j & 3) + 8 * (j >> 2) + 4 * hh;
-        if (q < mykey) p0 = 0.f;
-        if (q + 1 < mykey) p1 = 0.f;
+        if (q < mykey || (DOC && q >= de_my)) p0 = 0.f;
+        if (q + 1 < mykey || (DOC && q + 1 >= de_my)) p1 = 0.f;
       }
       pw[j >> 1] = pack2(p0, p1);
       sw[j >> 1] = pack2(p0 * dp[j], p1 * dp[j + 1]);
@@ -800,7 +848,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_kernel(
   auto step = [&](int it, int buf) {
     if (it + 1 < total) gload(it + 1);
     const int qs = (qt0 + it % nqt) * 64 + 32 * m;
-    if (qs > kw) subtile(buf, qs, false);        // strictly below this wave's diagonal
+    if constexpr (DOC) {
+      // sub-tiles past the wave's last document see none of its keys: not
+      // computed; one that reaches past some key's document is masked
+      if (qs > kw && qs < de_hi && qs + 32 <= de_lo) subtile(buf, qs, false);
+      else if (qs >= kw && qs < de_hi) subtile(buf, qs, true);
+    } else if (qs > kw) subtile(buf, qs, false);  // strictly below this wave's diagonal
     else if (qs == kw) subtile(buf, qs, true);  // the diagonal sub-tile
     if (it + 1 < total) swrite(buf ^ 1);
     __syncthreads();
@@ -873,12 +926,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_kernel(
 // the B operand straight from the accumulator.  K and V share the
 // one-image-two-ways layout (rt_off).
 // ---------------------------------------------------------------------------
-template <int D, bool TAIL>
+template <int D, bool TAIL, bool DOC = false>
 __global__ __launch_bounds__(512, 1) void attn_bwd_dq_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O, const float* __restrict__ LSE,
     float* __restrict__ DELTA, bf16_t* __restrict__ dQ, int B, int H, int Hk, int S, float scale, float scale_log2,
-    int o_bshd) {
+    int o_bshd, const int* __restrict__ DSTART = nullptr) {
   using G = AG<D>;
   constexpr int ROWB = G::ROWB, NCH = G::NCH, NS = G::NS, ND = G::ND, TILEB = G::TILEB;
   constexpr int NL = TK * NCH / 512;
@@ -898,6 +951,15 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq_kernel(
   const int kend = min(S, (qb + 1) * FWD_QB);
   const int ntiles = (kend + TK - 1) / TK;
   const int t_diag = live ? (q0 + 31) / TK : -1;
+  // document mask: as in attn_fwd_kernel
+  int t_beg = 0, t_lo = 0, ds_hi = 0, ds_my = 0;
+  if constexpr (DOC) {
+    const int* dsb = DSTART + (int64_t)b * S;
+    t_beg = doc_row_start(dsb, qb * FWD_QB, S) / TK;
+    t_lo = __builtin_amdgcn_readfirstlane(doc_row_start(dsb, q0, S)) / TK;
+    ds_hi = __builtin_amdgcn_readfirstlane(doc_row_start(dsb, q0 + 31, S));
+    ds_my = doc_row_start(dsb, myq, S);
+  }
 
   bf16x8 qf[NS], of[NS];
 #pragma unroll
@@ -985,8 +1047,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq_kernel(
         float p1 = EXP2(x[1]);
         if (mask) {
           const int key = t * TK + 32 * n + (j & 3) + 8 * (j >> 2) + 4 * hh;
-          if (key > myq) p0 = 0.f;
-          if (key + 1 > myq) p1 = 0.f;
+          if (key > myq || (DOC && key < ds_my)) p0 = 0.f;
+          if (key + 1 > myq || (DOC && key + 1 < ds_my)) p1 = 0.f;
         }
         const f32x2 d = (f32x2{dp[j], dp[j + 1]} - del2) * f32x2{p0, p1};
         sw[j >> 1] = pack2(d[0], d[1]);
@@ -1009,19 +1071,24 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq_kernel(
   };
   auto step = [&](int t, int buf) {
     if (t + 1 < ntiles) gload(t + 1);
-    if (t < t_diag) compute(t, buf, false);
-    else if (t == t_diag) compute(t, buf, true);
+    if constexpr (DOC) {
+      if (t >= t_lo && t < t_diag && t * TK >= ds_hi) compute(t, buf, false);
+      else if (t >= t_lo && t <= t_diag) compute(t, buf, true);
+    } else {
+      if (t < t_diag) compute(t, buf, false);
+      else if (t == t_diag) compute(t, buf, true);
+    }
     if (t + 1 < ntiles) swrite(buf ^ 1);
     __syncthreads();
   };
 
-  gload(0);
+  gload(t_beg);
   swrite(0);
 #pragma unroll
   for (int s = 0; s < NS; ++s) asm volatile("" ::"v"(qf[s]), "v"(of[s]));  // retire resident loads (see fwd)
   asm volatile("" ::"v"(lse2), "v"(del));
   __syncthreads();
-  int t = 0;
+  int t = t_beg;
   for (; t + 1 < ntiles; t += 2) {
     step(t, 0);
     step(t + 1, 1);
@@ -1692,6 +1759,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_ds_kernel(
     }
 }
 
+// Host side.  This file is compiled twice: as itself, with every unmasked entry
+// point, and through attention_doc.hip (TOA_ATTN_DOC_TU), with the document-mask
+// entry points alone -- the DOC instantiations then sit in a code object of
+// their own, and the one every unmasked call loads holds the kernels it held
+// before the mask existed.
+#ifndef TOA_ATTN_DOC_TU
 // Backward form: 1 = dS through HBM (default where S % 256 == 0: the
 // Llama-3-8B step 987.9 -> 978.1 ms, profiles/r3_attn_ds), 0 = split (dQ
 // recomputes S / dP; ragged S always).  TOA_ATTN_BWD=split|ds, or
@@ -1772,19 +1845,22 @@ extern "C" int64_t toa_attn_bwd_ws_bytes(int B, int H, int S, int D) {
   return attn_bwd_uses_ds(S) ? attn_ds_bytes(B, H, S) : 0;
 }
 
-template <int D, bool TAIL>
+#endif  // !TOA_ATTN_DOC_TU
+
+template <int D, bool TAIL, bool DOC = false>
 static void attn_set_lds_limits() {
   static bool done = false;
   if (done) return;
-  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, TAIL, DOC>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             4 * AG<D>::TILEB);
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            DKV<D>::LDS);
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D, TAIL, DOC>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, DKV<D>::LDS);
+  (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, TAIL, DOC>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             4 * AG<D>::TILEB);
   done = true;
 }
 
+#ifndef TOA_ATTN_DOC_TU
 // Forward form: 1 = LDS-DMA staged K/V (where S % 256 == 0: 0.868 -> 0.811
 // ms at the bench shape, bit-identical, profiles/r3_attn_ds), 0 = register
 // staged (ragged S always), 2 = the assembly kernel (csrc/asm/attn_gen.py;
@@ -1845,10 +1921,13 @@ static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, co
   return (int)hipGetLastError();
 }
 
+#endif  // !TOA_ATTN_DOC_TU
+
 static bool attn_shape_ok(int B, int H, int Hk, int S, int D, int flags) {
   return (D == 64 || D == 128) && B > 0 && S > 0 && Hk > 0 && H % Hk == 0 && (flags & 1);
 }
 
+#ifndef TOA_ATTN_DOC_TU
 // The assembly forward (csrc/asm/attn_gen.py, host side csrc/hip/gemm_asm.hip)
 // takes D = 128, S % 256 == 0; TOA_ATTN_FWD=hip keeps the HIP kernel (A/B).
 extern "C" int toa_attn_fwd_asm(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, int B,
@@ -1906,6 +1985,82 @@ extern "C" int toa_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, c
 #undef TOA_ATTN_BWD
 }
 
+#endif  // !TOA_ATTN_DOC_TU
+
+#ifdef TOA_ATTN_DOC_TU
+// Document-masked causal attention (packed sequences): the DOC arms of the
+// register-staged kernels, any S >= 1, both O layouts; a masked call never
+// reaches the assembly kernels, the LDS-DMA forward or the dS form.
+// doc_start / doc_end int32 [B, S], non-decreasing along a row: the first
+// position of the document holding position i, and one past its last.
+// Backward: dQ (which also writes delta) on doc_start, then dK/dV on doc_end.
+template <int D, bool TAIL>
+static int attn_fwd_doc_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse,
+                               const int* doc_start, int B, int H, int Hk, int S, int o_bshd, float scale,
+                               hipStream_t stream) {
+  attn_set_lds_limits<D, TAIL, true>();
+  hipLaunchKernelGGL((attn_fwd_kernel<D, TAIL, true>), dim3(((S + FWD_QB - 1) / FWD_QB) * H * B),
+                     dim3(64 * FWD_WAVES), 4 * AG<D>::TILEB, stream, q, k, v, o, lse, B, H, Hk, S, scale * LOG2E, o_bshd,
+                     doc_start);
+  return (int)hipGetLastError();
+}
+
+template <int D, bool TAIL>
+static int attn_bwd_doc_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                               const float* lse, float* delta, const int* doc_start, const int* doc_end, bf16_t* dq,
+                               bf16_t* dk, bf16_t* dv, int B, int H, int Hk, int S, int o_bshd, float scale,
+                               hipStream_t stream) {
+  attn_set_lds_limits<D, TAIL, true>();
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, TAIL, true>), dim3(((S + FWD_QB - 1) / FWD_QB) * H * B),
+                     dim3(64 * FWD_WAVES), 4 * AG<D>::TILEB, stream, q, k, v, dout, o, lse, delta, dq, B, H, Hk, S, scale,
+                     scale * LOG2E, o_bshd, doc_start);
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, TAIL, true>), dim3(((S + 127) / 128) * B * Hk), dim3(512), DKV<D>::LDS,
+                     stream, q, k, v, dout, lse, delta, dk, dv, B, H, Hk, S, scale, scale * LOG2E, o_bshd, doc_end);
+  return (int)hipGetLastError();
+}
+
+extern "C" int toa_attn_fwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse,
+                                const int* doc_start, int B, int H, int Hk, int S, int D, int flags, float scale,
+                                hipStream_t stream) {
+  if (!attn_shape_ok(B, H, Hk, S, D, flags) || doc_start == nullptr) return (int)hipErrorInvalidValue;
+  const int o_bshd = (flags >> 1) & 1;
+  const bool tail = S % FWD_QB != 0;
+#define TOA_ATTN_FWD_DOC(DD, TT) \
+  attn_fwd_doc_launch<DD, TT>(q, k, v, o, lse, doc_start, B, H, Hk, S, o_bshd, scale, stream)
+#ifdef TOA_ATTN_D128_ONLY
+  if (D != 128) return (int)hipErrorInvalidValue;
+  return tail ? TOA_ATTN_FWD_DOC(128, true) : TOA_ATTN_FWD_DOC(128, false);
+#else
+  if (D == 128) return tail ? TOA_ATTN_FWD_DOC(128, true) : TOA_ATTN_FWD_DOC(128, false);
+  return tail ? TOA_ATTN_FWD_DOC(64, true) : TOA_ATTN_FWD_DOC(64, false);
+#endif
+#undef TOA_ATTN_FWD_DOC
+}
+
+extern "C" int toa_attn_bwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o,
+                                const bf16_t* dout, const float* lse, float* delta, const int* doc_start,
+                                const int* doc_end, bf16_t* dq, bf16_t* dk, bf16_t* dv, int B, int H, int Hk, int S,
+                                int D, int flags, float scale, hipStream_t stream) {
+  if (!attn_shape_ok(B, H, Hk, S, D, flags) || doc_start == nullptr || doc_end == nullptr)
+    return (int)hipErrorInvalidValue;
+  const int o_bshd = (flags >> 1) & 1;
+  const bool tail = S % FWD_QB != 0;
+#define TOA_ATTN_BWD_DOC(DD, TT)                                                                                   \
+  attn_bwd_doc_launch<DD, TT>(q, k, v, o, dout, lse, delta, doc_start, doc_end, dq, dk, dv, B, H, Hk, S, o_bshd, \
+                              scale, stream)
+#ifdef TOA_ATTN_D128_ONLY
+  if (D != 128) return (int)hipErrorInvalidValue;
+  return tail ? TOA_ATTN_BWD_DOC(128, true) : TOA_ATTN_BWD_DOC(128, false);
+#else
+  if (D == 128) return tail ? TOA_ATTN_BWD_DOC(128, true) : TOA_ATTN_BWD_DOC(128, false);
+  return tail ? TOA_ATTN_BWD_DOC(64, true) : TOA_ATTN_BWD_DOC(64, false);
+#endif
+#undef TOA_ATTN_BWD_DOC
+}
+
+#endif  // TOA_ATTN_DOC_TU
+
+#ifndef TOA_ATTN_DOC_TU
 // Fused RoPE + attention backward (the dS form only: S % 256 == 0, packed
 // K/V = one copy per kv head): d(qkv) [B*S, (H + 2 Hk) * D] straight from the
 // dQ GEMM's and the dK/dV kernel's epilogues, rotated back with cos / sin
@@ -1958,3 +2113,4 @@ extern "C" int toa_attn_bwd_rope(const bf16_t* q, const bf16_t* k, const bf16_t*
 #undef TOA_ATTN_BWD_ROPE
   return (int)hipGetLastError();
 }
+#endif  // !TOA_ATTN_DOC_TU

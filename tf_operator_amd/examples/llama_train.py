@@ -40,7 +40,21 @@ def main(argv=None):
                         "(default: TOA_ADAM_STATE, else fp32)")
     p.add_argument("--zero-check", action="store_true", default=None,
                    help="raise on a weight read whose ZeRO-1 all-gather was not waited for (default: TOA_ZERO_CHECK)")
+    p.add_argument("--doc-mask", action="store_true",
+                   help="pack rows from documents ending with --eos-id and keep attention inside each document")
+    p.add_argument("--eos-id", type=int, default=0, help="the end-of-document token id of --doc-mask")
+    p.add_argument("--doc-len", dest="doc_len_arg", default="16:128", metavar="LO:HI",
+                   help="document lengths of the synthetic stream under --doc-mask")
     a = p.parse_args(argv)
+    a.doc_len = None
+    if a.doc_mask:
+        try:
+            lo, hi = (int(x) for x in a.doc_len_arg.split(":"))
+        except ValueError:
+            p.error("--doc-len takes LO:HI")
+        if not 1 <= lo <= hi:
+            p.error("--doc-len needs 1 <= LO <= HI")
+        a.doc_len = (lo, hi)
     from tf_operator_amd.ops import gemm
 
     gemm.prewarm_early()  # GEMM plans resolve while the process group and the model come up
@@ -69,7 +83,7 @@ def _train(a, rt, info):
     dev = pick_device() if info.backend != "gloo" or os.environ.get("TOA_DIST_BACKEND") else torch.device("cpu")
     zero = rt.world > 1 if a.zero == "auto" else a.zero == "1"
     tr = LlamaTrainer(a.model, dev, micro_batch=a.micro_batch, seq_len=a.seq_len, lr=a.lr, shard_optimizer=zero,
-                      adam_state=a.adam_state, zero_check=a.zero_check)
+                      adam_state=a.adam_state, zero_check=a.zero_check, doc_eos=a.eos_id if a.doc_mask else None)
     rt.mark("model_init")
     tr.on_phase = rt.mark  # the first step's host-side issue points, in the start-up phases
     ck = sharded_ckpt.Checkpointer(rt.ckpt_dir, rt.rank, rt.world) if rt.ckpt_dir else None
@@ -78,7 +92,7 @@ def _train(a, rt, info):
     # a resumable stream: batch i of rank r is a function of (seed, r, i), so
     # the checkpointed cursor continues the uninterrupted run's data exactly
     data = SyntheticTokens(a.micro_batch, a.seq_len, tr.cfg.vocab_size, rank=rt.rank, device=dev,
-                           fixed=a.fixed_batch)
+                           fixed=a.fixed_batch, doc_len=a.doc_len, eos_id=a.eos_id if a.doc_mask else None)
     shares = sharded_ckpt.load_latest(rt.ckpt_dir)
     if shares is not None:
         load_trainer_state(tr, shares, data=data)  # re-shards a checkpoint of any world size

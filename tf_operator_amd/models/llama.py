@@ -96,7 +96,7 @@ class LlamaBlock(torch.nn.Module):
     def params_backward_order(self):
         return [self.wd, self.wgu, self.mlp_norm.weight, self.wo, self.wqkv, self.attn_norm.weight]
 
-    def forward(self, h, delta, cos, sin, B, S, cossin=None):
+    def forward(self, h, delta, cos, sin, B, S, cossin=None, doc=None):
         cfg = self.cfg
         if delta is None:
             x = self.attn_norm(h)
@@ -105,7 +105,7 @@ class LlamaBlock(torch.nn.Module):
         else:
             h, x = self.attn_norm(h, delta)
         a, summed = attention_block(x, self.wqkv, self.wo, cos, sin, B, S, cfg.heads, cfg.kv_heads, cfg.head_dim,
-                                    residual=h, kv_layout=cfg.kv_layout, cossin=cossin)
+                                    residual=h, kv_layout=cfg.kv_layout, cossin=cossin, doc=doc)
         # summed: the output projection's epilogue added the residual; the norm then reads the sum once
         h, x = self.mlp_norm.presummed(a) if summed else self.mlp_norm(h, a)
         if swiglu_mlp_resadd_ok(x, self.wd, h):
@@ -166,13 +166,16 @@ class Llama(torch.nn.Module):
             self._rope_cache[key] = (cos, sin, rope_cossin(cos, sin))
         return self._rope_cache[key]
 
-    def forward(self, tokens, targets=None):
+    def forward(self, tokens, targets=None, doc=None):
+        """doc: the (doc_start, doc_end) pair of ops.llm.doc_bounds for these
+        tokens; every block's attention then stays inside each document
+        (RoPE positions stay the row's).  None: plain causal attention."""
         B, S = tokens.shape
         cos, sin, cossin = self.rope(S, tokens.device)
         h = self.embed(tokens).view(B * S, self.cfg.hidden)
         delta = None
         for blk in self.blocks:
-            h, delta = blk(h, delta, cos, sin, B, S, cossin)
+            h, delta = blk(h, delta, cos, sin, B, S, cossin, doc)
         _, x = self.norm.presummed(h) if delta is PRESUMMED else self.norm(h, delta)
         head = self.head_weight()
         reading(head, "lm_head")   # waited for by the final norm's hook (train/llm.py _install_param_waits)

@@ -359,6 +359,117 @@ def _attn_bwd(q, k, v, o, lse, do, scale, bshd):
     return dq, dk, dv
 
 
+# ---------------------------------------------------------------------------
+# Document mask (packed sequences): query i sees key j iff doc_start[i] <= j <= i
+# ---------------------------------------------------------------------------
+def doc_bounds(tokens, eos_id):
+    """(doc_start, doc_end), int32 [B, S] on the tokens' device, of rows
+    packed from documents that each end with ``eos_id``: doc_start[b, i] is
+    the first position of the document holding position i, doc_end[b, i] one
+    past its last.  An EOS token belongs to the document it ends; the next
+    document starts at the following position.  A row's last document ends
+    at S whether or not an EOS closes it."""
+    B, S = tokens.shape
+    pos = torch.arange(S, device=tokens.device, dtype=torch.int64).expand(B, S)
+    eos = tokens == eos_id
+    first = torch.ones_like(eos)     # position 0 and every position after an EOS open a document
+    first[:, 1:] = eos[:, :-1]
+    last = eos.clone()               # every EOS and position S - 1 close one
+    last[:, -1] = True
+    start = torch.where(first, pos, torch.zeros_like(pos)).cummax(1).values
+    end = torch.where(last, pos + 1, torch.full_like(pos, S)).flip(1).cummin(1).values.flip(1)
+    return start.to(torch.int32).contiguous(), end.to(torch.int32).contiguous()
+
+
+def doc_bounds_from_lengths(lengths_per_row, S, device=None):
+    """The same pair from explicit boundaries: one list of document lengths
+    per row, each list positive and summing to S."""
+    starts, ends = [], []
+    for lens in lengths_per_row:
+        lens = [int(n) for n in lens]
+        if not lens or min(lens) < 1 or sum(lens) != S:
+            raise ValueError(f"document lengths {lens} must be positive and sum to {S}")
+        n = torch.tensor(lens, dtype=torch.int64)
+        e = n.cumsum(0)
+        starts.append(torch.repeat_interleave(e - n, n))
+        ends.append(torch.repeat_interleave(e, n))
+    return (torch.stack(starts).to(device=device, dtype=torch.int32).contiguous(),
+            torch.stack(ends).to(device=device, dtype=torch.int32).contiguous())
+
+
+def _check_doc(doc, B, S, device):
+    ds, de = doc
+    for name, t in (("doc_start", ds), ("doc_end", de)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, S) or t.device != device or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [{B}, {S}] tensor on {device} "
+                             f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+    return ds, de
+
+
+def _attn_fwd_doc(q, k, v, ds, scale, bshd):
+    """toa_attn_fwd_doc: _attn_fwd under the document mask."""
+    B, H, S, D = q.shape
+    o = torch.empty(B, S, H, D, device=q.device, dtype=q.dtype) if bshd else torch.empty_like(q)
+    lse = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
+    _lib.call("toa_attn_fwd_doc", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(ds),
+              B, H, k.shape[1], S, D, 1 | (2 if bshd else 0), float(scale), _lib.stream(q))
+    return o, lse
+
+
+def _attn_bwd_doc(q, k, v, o, lse, do, ds, de, scale, bshd):
+    """toa_attn_bwd_doc: the two-kernel backward (dQ, which also computes
+    delta, then dK/dV) under the document mask; no workspace."""
+    B, H, S, D = q.shape
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
+    _lib.call("toa_attn_bwd_doc", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(do), _lib.ptr(lse),
+              _lib.ptr(delta), _lib.ptr(ds), _lib.ptr(de), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), B, H, k.shape[1],
+              S, D, 1 | (2 if bshd else 0), float(scale), _lib.stream(q))
+    return dq, dk, dv
+
+
+class _FlashAttnDoc(torch.autograd.Function):
+    """_FlashAttn under a document mask (toa_attn_fwd_doc / toa_attn_bwd_doc)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, ds, de, scale, bshd=False):
+        o, lse = _attn_fwd_doc(q, k, v, ds, scale, bshd)
+        ctx.save_for_backward(q, k, v, o, lse, ds, de)
+        ctx.scale = scale
+        ctx.bshd = bshd
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, ds, de = ctx.saved_tensors
+        return (*_attn_bwd_doc(q, k, v, o, lse, do.contiguous(), ds, de, ctx.scale, ctx.bshd), None, None, None, None)
+
+
+class _RopeAttnDoc(torch.autograd.Function):
+    """_RopeAttn under a document mask.  Backward: toa_attn_bwd_doc, then RoPE
+    backward as its own pass (toa_rope_bwd) -- the fused epilogues belong to
+    the dS form, which carries no mask."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, ds, de, B, S, Hq, Hkv, D, scale, bshd):
+        q, k, v = _rope_fwd(qkv, cos, sin, B, S, Hq, Hkv, D, 1)
+        o, lse = _attn_fwd_doc(q, k, v, ds, scale, bshd)
+        ctx.save_for_backward(q, k, v, o, lse, cos, sin, ds, de)
+        ctx.scale, ctx.bshd = scale, bshd
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, cos, sin, ds, de = ctx.saved_tensors
+        B, Hq, S, D = q.shape
+        Hkv = k.shape[1]
+        dq, dk, dv = _attn_bwd_doc(q, k, v, o, lse, do.contiguous(), ds, de, ctx.scale, ctx.bshd)
+        dqkv = torch.empty(B * S, (Hq + 2 * Hkv) * D, device=q.device, dtype=q.dtype)
+        _lib.call("toa_rope_bwd", _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(cos), _lib.ptr(sin),
+                  _lib.ptr(dqkv), B, S, Hq, Hkv, D, 1, _lib.stream(q))
+        return (dqkv,) + (None,) * 11
+
+
 # TOA_ATTN_ROPE_FUSED=0: RoPE backward as its own pass even where the fused
 # epilogues could take it (A/B)
 _ROPE_FUSED_BWD = os.environ.get("TOA_ATTN_ROPE_FUSED", "1") != "0"
@@ -571,12 +682,18 @@ def qkv_rope_attention(x, wqkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layo
     return _QKVRopeAttn.apply(x, wqkv, cos, sin, cossin, B, S, Hq, Hkv, D, scale, out_layout == "bshd", link)
 
 
-def rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd", link=None):
+def rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd", link=None, doc=None):
     """RoPE (Llama rotate-half, cos / sin [S, D/2]) on the fused QKV
     projection [B*S, (Hq + 2 Hkv) D], then causal attention with packed GQA:
     O as [B, S, Hq, D] (out_layout="bshd") or [B, Hq, S, D].  On the GPU one
     autograd node (_RopeAttn) whose backward writes d(qkv) directly (link: see
-    attn_out_proj); on the CPU rope_qkv + causal_attention."""
+    attn_out_proj); on the CPU rope_qkv + causal_attention.
+
+    doc: the (doc_start, doc_end) pair of doc_bounds; attention then stays
+    inside each document (a node of its own, _RopeAttnDoc; link is not used).
+    RoPE positions stay global, the row's: RoPE is relative, a score depends
+    on the distance between query and key only, so scores inside a document
+    do not depend on where the document sits in the row."""
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     if qkv.is_cuda:
         if not (qkv.dtype == torch.bfloat16 and D in ATTN_HEAD_DIMS and _lib.has("toa_attn_fwd")
@@ -585,19 +702,36 @@ def rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, scale=None, out_layout="bshd
                                f"(got {qkv.dtype}, head_dim {D}; library: {_lib.load_error() or 'ok'})")
         if Hq % Hkv:
             raise ValueError(f"query heads {Hq} not a multiple of kv heads {Hkv}")
+        if doc is not None:
+            ds, de = _check_doc(doc, B, S, qkv.device)
+            return _RopeAttnDoc.apply(qkv, cos, sin, ds, de, B, S, Hq, Hkv, D, scale, out_layout == "bshd")
         return _RopeAttn.apply(qkv, cos, sin, B, S, Hq, Hkv, D, scale, out_layout == "bshd", link)
     q, k, v = rope_qkv(qkv, cos, sin, B, S, Hq, Hkv, D, 1)
-    return causal_attention(q, k, v, scale, out_layout)
+    return causal_attention(q, k, v, scale, out_layout, doc=doc)
 
 
-def attention_block(x, wqkv, wo, cos, sin, B, S, Hq, Hkv, D, residual=None, kv_layout="auto", cossin=None):
+def attention_block(x, wqkv, wo, cos, sin, B, S, Hq, Hkv, D, residual=None, kv_layout="auto", cossin=None, doc=None):
     """QKV projection, RoPE, causal attention and output projection on the
     normalised x [B S, hidden].  Returns (out, summed): summed where the
     projection's epilogue added the residual (else the caller's norm adds it).
     Packed K/V: one node for projection + RoPE + attention where
     qkv_rope_attention_ok, else linear + rope_attention, sharing a _DeltaLink
-    with the output projection on the GPU; "expand": K/V per query head."""
+    with the output projection on the GPU; "expand": K/V per query head.
+
+    doc: the (doc_start, doc_end) pair of doc_bounds.  The masked block takes
+    linear + rope_attention (RoPE positions stay global, see there) with no
+    _DeltaLink: its two-kernel backward computes delta itself and RoPE
+    backward is its own pass."""
     packed = kv_layout in ("packed", "auto")
+    if doc is not None:
+        if packed:
+            o = rope_attention(linear(x, wqkv), cos, sin, B, S, Hq, Hkv, D, doc=doc)
+        else:
+            q, k, v = rope_qkv(linear(x, wqkv), cos, sin, B, S, Hq, Hkv, D)
+            o = causal_attention(q, k, v, out_layout="bshd", doc=doc)
+        o = o.reshape(B * S, Hq * D)
+        summed = residual is not None and packed and x.is_cuda and attn_out_proj_resadd_ok(o, wo, residual)
+        return attn_out_proj(o, wo, B, S, Hq, residual if summed else None, None), summed
     link = _DeltaLink() if packed and x.is_cuda else None
     if packed and qkv_rope_attention_ok(x, wqkv, S, Hq, Hkv, D):
         o = qkv_rope_attention(x, wqkv, cos, sin, B, S, Hq, Hkv, D, cossin=cossin, link=link)
@@ -611,9 +745,28 @@ def attention_block(x, wqkv, wo, cos, sin, B, S, Hq, Hkv, D, residual=None, kv_l
     return attn_out_proj(o, wo, B, S, Hq, residual if summed else None, link), summed
 
 
-def _attention_reference(q, k, v, scale):
+def _doc_segments(doc_start_row):
+    """[(first, one past last)] of the documents of one row's doc_start."""
+    vals, counts = torch.unique_consecutive(doc_start_row.to(torch.int64), return_counts=True)
+    ends = counts.cumsum(0)
+    if not torch.equal(vals, ends - counts):
+        raise ValueError("doc_start is not the first position of each position's document")
+    return list(zip(vals.tolist(), ends.tolist()))
+
+
+def _attention_reference(q, k, v, scale, doc=None):
     """Plain PyTorch causal attention (fp32 math, packed GQA expanded): the
-    CPU path and the numerics reference of the HIP kernel."""
+    CPU path and the numerics reference of the HIP kernel.  doc: the
+    (doc_start, doc_end) pair; query i sees key j iff doc_start[i] <= j <= i.
+    That mask is block diagonal, and it is evaluated block by block: each
+    document alone through the unmasked computation, so a document's rows
+    are bit for bit what the document gives on its own, wherever it sits."""
+    if doc is not None:
+        rows = []
+        for b in range(q.shape[0]):
+            rows.append(torch.cat([_attention_reference(q[b:b + 1, :, a:e], k[b:b + 1, :, a:e], v[b:b + 1, :, a:e], scale)
+                                   for a, e in _doc_segments(doc[0][b])], 2))
+        return torch.cat(rows, 0)
     rep = q.shape[1] // k.shape[1]
     if rep > 1:
         k = k.repeat_interleave(rep, 1)
@@ -624,9 +777,11 @@ def _attention_reference(q, k, v, scale):
     return torch.matmul(torch.softmax(s, -1), v.float()).to(q.dtype)
 
 
-def causal_attention(q, k, v, scale=None, out_layout="bhsd"):
+def causal_attention(q, k, v, scale=None, out_layout="bhsd", doc=None):
     """q [B,H,S,D], k/v [B,Hk,S,D] (packed GQA, H % Hk == 0), any S.
     Returns O as [B,H,S,D], or as [B,S,H,D] with out_layout="bshd".
+    doc: the (doc_start, doc_end) pair of doc_bounds (int32 [B, S] each):
+    query i then sees key j iff doc_start[i] <= j <= i.
 
     On a GPU tensor this is ALWAYS the HIP flash-attention kernel (bf16,
     head_dim 64 or 128); anything else raises -- there is no library
@@ -638,6 +793,10 @@ def causal_attention(q, k, v, scale=None, out_layout="bhsd"):
                                f"(got {q.dtype}, head_dim {q.shape[-1]}; library: {_lib.load_error() or 'ok'})")
         if q.shape[1] % k.shape[1]:
             raise ValueError(f"query heads {q.shape[1]} not a multiple of kv heads {k.shape[1]}")
+        if doc is not None:
+            ds, de = _check_doc(doc, q.shape[0], q.shape[2], q.device)
+            return _FlashAttnDoc.apply(q.contiguous(), k.contiguous(), v.contiguous(), ds, de, scale,
+                                       out_layout == "bshd")
         return _FlashAttn.apply(q.contiguous(), k.contiguous(), v.contiguous(), scale, out_layout == "bshd")
-    o = _attention_reference(q, k, v, scale)
+    o = _attention_reference(q, k, v, scale, doc)
     return o.transpose(1, 2) if out_layout == "bshd" else o

@@ -99,18 +99,48 @@ class SyntheticTokens:
     reads exactly the batches the uninterrupted run would have read next.
 
     ``fixed=True`` hands out batch 0 every time (the benchmark's resident
-    batch: no generation work inside the timed step)."""
+    batch: no generation work inside the timed step).
 
-    def __init__(self, micro_batch, seq_len, vocab, rank=0, seed=100, device="cpu", fixed=False):
+    ``doc_len=(lo, hi)`` with ``eos_id`` packs each row from documents: the
+    stream of seq_len + 1 tokens is cut into pieces of lo..hi tokens, lengths
+    drawn from the batch's own generator after its tokens, each piece ending
+    with ``eos_id``; no other position holds ``eos_id``.  The batch stays a
+    pure function of (seed, rank, i) and the cursor is still the whole state."""
+
+    def __init__(self, micro_batch, seq_len, vocab, rank=0, seed=100, device="cpu", fixed=False, doc_len=None,
+                 eos_id=None):
         self.micro_batch, self.seq_len, self.vocab = micro_batch, seq_len, vocab
         self.rank, self.seed, self.device, self.fixed = rank, seed, torch.device(device), fixed
+        if (doc_len is None) != (eos_id is None):
+            raise ValueError("doc_len and eos_id go together")
+        if doc_len is not None:
+            lo, hi = int(doc_len[0]), int(doc_len[1])
+            if not 1 <= lo <= hi:
+                raise ValueError(f"doc_len {doc_len!r}: need 1 <= lo <= hi")
+            if not 0 <= int(eos_id) < vocab or vocab < 2:
+                raise ValueError(f"eos_id {eos_id} is not a token id of a vocabulary of {vocab}")
+            doc_len, eos_id = (lo, hi), int(eos_id)
+        self.doc_len, self.eos_id = doc_len, eos_id
         self.cursor = 0
         self._fixed = None
 
     def _draw(self, i):
         g = torch.Generator(device=self.device)
         g.manual_seed((self.seed * 1000003 + self.rank) * 1000003 + i)
-        tok = torch.randint(0, self.vocab, (self.micro_batch, self.seq_len + 1), device=self.device, generator=g)
+        n = self.seq_len + 1
+        if self.doc_len is None:
+            tok = torch.randint(0, self.vocab, (self.micro_batch, n), device=self.device, generator=g)
+        else:
+            lo, hi = self.doc_len
+            # ordinary tokens skip eos_id: draw from vocab - 1 ids and shift those at or above it
+            tok = torch.randint(0, self.vocab - 1, (self.micro_batch, n), device=self.device, generator=g)
+            tok = tok + (tok >= self.eos_id).to(tok.dtype)
+            # enough lengths to cover the row even if every one is lo; the last position of each piece is its EOS
+            lens = torch.randint(lo, hi + 1, (self.micro_batch, (n + lo - 1) // lo), device=self.device, generator=g)
+            ends = lens.cumsum(1) - 1
+            rows = torch.arange(self.micro_batch, device=self.device)[:, None].expand_as(ends)
+            keep = ends < n
+            tok[rows[keep], ends[keep]] = self.eos_id
         return tok[:, :-1].contiguous(), tok[:, 1:].contiguous()
 
     def next(self):

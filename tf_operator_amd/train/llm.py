@@ -22,6 +22,7 @@ import time
 import torch
 
 from ..models.llama import PRESETS, Llama, LlamaConfig
+from ..ops.llm import doc_bounds
 from ..ops.optim import FlatAdamW
 from ..ops.wt import TransposedWeights, enabled_default
 from ..parallel.ddp import GradBucketer, broadcast_params
@@ -35,9 +36,16 @@ class LlamaTrainer:
     def __init__(self, cfg: LlamaConfig | str, device, micro_batch=1, seq_len=4096, grad_accum=1, lr=3e-4,
                  seed=0, bucket_mb=None, overlap_optimizer=None, shard_optimizer=None,
                  transposed_weights=None, force_collectives=False, adam_state=None, zero_check=None,
-                 zero_poison=None, zero_ag_delay_us=None):
+                 zero_poison=None, zero_ag_delay_us=None, doc_eos=None):
         if isinstance(cfg, str):
             cfg = PRESETS[cfg]
+        # doc_eos: a token id.  Each micro-batch's rows are then taken as documents that end with that
+        # token, and attention stays inside each document (ops.llm.doc_bounds, the masked attention
+        # kernels).  Targets are left as they are: the EOS position still predicts the next document's
+        # first token, as in the unmasked stream (no loss mask at boundaries).  None: plain causal rows.
+        if doc_eos is not None and not 0 <= int(doc_eos) < cfg.vocab_size:
+            raise ValueError(f"doc_eos {doc_eos} is not a token id of a vocabulary of {cfg.vocab_size}")
+        self.doc_eos = None if doc_eos is None else int(doc_eos)
         # adam_state: "fp32" or "bf16" AdamW moments (None: TOA_ADAM_STATE, default fp32).  bf16 halves
         # the moments' traffic and footprint; stochastically rounded (ops/optim.py FlatAdamW state_dtype)
         if adam_state is None:
@@ -205,7 +213,10 @@ class LlamaTrainer:
             self.flat.zero_grad()
         loss_sum = None
         for i, (tok, tgt) in enumerate(batches):
-            loss = self.model(tok, tgt)
+            if self.doc_eos is None:
+                loss = self.model(tok, tgt)
+            else:
+                loss = self.model(tok, tgt, doc=doc_bounds(tok, self.doc_eos))
             self._phase("first_fwd_issued")
             self.opt.wait_all()  # backward writes gradients the update is still zeroing
             if self.gather is not None:

@@ -230,10 +230,49 @@ __device__ __forceinline__ void sr_pack8(const float* mm, const float* vv, int64
   }
 }
 
+// ---------------------------------------------------------------------------
+// Skipped steps (FlatAdamW skip_nonfinite): one verdict per step, taken on
+// the device after the gradient norm is final and obeyed by every AdamW launch
+// of that step.  flag[0] != 0: the step is skipped (the norm is Inf / NaN, or
+// above `limit` where limit > 0).  skipped[0] counts the skipped steps, this
+// one included, so the launches of an applied step see the earlier ones only.
+// ---------------------------------------------------------------------------
+__global__ void adamw_guard_kernel(const float* __restrict__ norm_sq, float grad_scale, float limit,
+                                   int* __restrict__ flag, int* __restrict__ skipped) {
+  const float ns = norm_sq[0];
+  // the exponent test, not isfinite(): it holds under any floating-point flags
+  const bool bad = (__float_as_uint(ns) & 0x7f800000u) == 0x7f800000u;
+  const int f = (bad || (limit > 0.f && sqrtf(ns) * grad_scale > limit)) ? 1 : 0;
+  flag[0] = f;
+  skipped[0] += f;
+}
+
+extern "C" int toa_adamw_guard(const float* norm_sq, float grad_scale, float limit, int* flag, int* skipped,
+                               hipStream_t stream) {
+  if (norm_sq == nullptr || flag == nullptr || skipped == nullptr) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(adamw_guard_kernel, dim3(1), dim3(1), 0, stream, norm_sq, grad_scale, limit, flag, skipped);
+  return (int)hipGetLastError();
+}
+
+// The GUARD arm's step: host step minus the skipped ones.  With none skipped
+// the host's bias corrections are kept as they are (bit for bit the unguarded
+// kernel); otherwise both are recomputed in adam_prologue's step_dev form.
+__device__ __forceinline__ int guard_step(int step, const int* skipped, float b1, float b2, float& inv_bc1,
+                                          float& inv_sqrt_bc2) {
+  const int sk = skipped[0];
+  if (sk != 0) {
+    const float st = (float)(step - sk);
+    inv_bc1 = 1.f / (1.f - powf(b1, st));
+    inv_sqrt_bc2 = 1.f / sqrtf(1.f - powf(b2, st));
+  }
+  return step - sk;
+}
+
 // MT: the moments' storage type, float (16 B of the 28 B / parameter) or
 // bf16_t (8 of 20).  base / seed / step feed the rounding of bf16 moments
-// only; the fp32 instantiations ignore them.
-template <bool GRAD_BF16, bool NT, typename MT = float>
+// only; the fp32 instantiations ignore them.  GUARD: flag / skipped are read
+// (see above); a skipped step only zeroes its gradient slice, if asked to.
+template <bool GRAD_BF16, bool NT, typename MT = float, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ master, bf16_t* __restrict__ param,
                                                          void* __restrict__ grad, int zero_grad, MT* __restrict__ m,
                                                          MT* __restrict__ v, int64_t n8, float lr, float b1,
@@ -241,8 +280,20 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ mas
                                                          float inv_sqrt_bc2, float grad_scale,
                                                          const float* __restrict__ norm_sq, float max_norm,
                                                          const int* __restrict__ step_dev, int step, int64_t base,
-                                                         uint32_t seed) {
+                                                         uint32_t seed, const int* __restrict__ flag,
+                                                         const int* __restrict__ skipped) {
   constexpr bool MB = sizeof(MT) == 2;   // bf16 moments
+  if constexpr (GUARD) {
+    if (flag[0] != 0) {   // the same word for every workgroup: the whole grid leaves here
+      if (zero_grad) {
+        const int64_t nz = GRAD_BF16 ? n8 : 2 * n8;   // 16-byte pieces of the gradient slice
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nz; i += (int64_t)gridDim.x * blockDim.x)
+          *((u32x4*)grad + i) = u32x4{0, 0, 0, 0};
+      }
+      return;
+    }
+    step = guard_step(step, skipped, b1, b2, inv_bc1, inv_sqrt_bc2);
+  }
   const float scale = adam_prologue(b1, b2, grad_scale, norm_sq, max_norm, step_dev, inv_bc1, inv_sqrt_bc2);
   const float omb1 = 1.f - b1, omb2 = 1.f - b2, lrwd = lr * wd;
   const uint32_t key = MB ? sr_key(step_dev != nullptr ? step_dev[0] : step, seed) : 0u;
@@ -326,7 +377,7 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ mas
 // ---------------------------------------------------------------------------
 // MT = bf16_t: bf16 moments, rounded by sr_pack8 with the flat index base +
 // (the element's offset in the weight) -- the bits of the flat kernel.
-template <typename MT = float>
+template <typename MT = float, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ master, bf16_t* __restrict__ param,
                                                        bf16_t* __restrict__ grad, int zero_grad,
                                                        MT* __restrict__ m, MT* __restrict__ v,
@@ -334,9 +385,21 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
                                                        float b1, float b2, float eps, float wd, float inv_bc1,
                                                        float inv_sqrt_bc2, float grad_scale,
                                                        const float* __restrict__ norm_sq, float max_norm, int step,
-                                                       int64_t base, uint32_t seed) {
+                                                       int64_t base, uint32_t seed, const int* __restrict__ flag,
+                                                       const int* __restrict__ skipped) {
   constexpr bool MB = sizeof(MT) == 2;
   __shared__ u32x4 tile[128 * 16];
+  if constexpr (GUARD) {
+    if (flag[0] != 0) {   // skipped step: no update and no W^T tile; the weight's gradient is contiguous
+      if (zero_grad) {
+        const int64_t nz = (int64_t)R * C / 8;
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nz; i += (int64_t)gridDim.x * blockDim.x)
+          st16(grad + i * 8, u32x4{0, 0, 0, 0});
+      }
+      return;
+    }
+    step = guard_step(step, skipped, b1, b2, inv_bc1, inv_sqrt_bc2);
+  }
   const float scale = adam_prologue(b1, b2, grad_scale, norm_sq, max_norm, nullptr, inv_bc1, inv_sqrt_bc2);
   const float omb1 = 1.f - b1, omb2 = 1.f - b2, lrwd = lr * wd;
   const uint32_t key = MB ? sr_key(step, seed) : 0u;
@@ -430,11 +493,13 @@ __global__ __launch_bounds__(256) void adamw_wt_kernel(float* __restrict__ maste
   }
 }
 
-template <typename MT>
+template <typename MT, bool GUARD = false>
 static int adamw_wt_launch(float* master, bf16_t* param, bf16_t* grad, int zero_grad, MT* m, MT* v, bf16_t* wt,
                            int64_t ldt, int R, int C, float lr, float beta1, float beta2, float eps,
                            float weight_decay, int step, float grad_scale, const float* norm_sq, float max_norm,
-                           int64_t base, uint32_t seed, hipStream_t stream) {
+                           int64_t base, uint32_t seed, hipStream_t stream, const int* flag = nullptr,
+                           const int* skipped = nullptr) {
+  if (GUARD && (flag == nullptr || skipped == nullptr)) return (int)hipErrorInvalidValue;
   if (R <= 0 || C <= 0 || R % 128 || C % 128 || ldt < R || ldt % 8 || ((uintptr_t)master & 15) ||
       ((uintptr_t)m & 15) || ((uintptr_t)v & 15) || ((uintptr_t)grad & 15) || ((uintptr_t)param & 15) ||
       ((uintptr_t)wt & 15) || step < 1 || base < 0 || base % 8)
@@ -443,9 +508,9 @@ static int adamw_wt_launch(float* master, bf16_t* param, bf16_t* grad, int zero_
   const float inv_sqrt_bc2 = 1.f / sqrtf(1.f - powf(beta2, (float)step));
   const int64_t tiles = (int64_t)(R / 128) * (C / 128);
   const int grid = (int)(tiles < 16384 ? tiles : 16384);
-  hipLaunchKernelGGL(adamw_wt_kernel<MT>, dim3(grid), dim3(256), 0, stream, master, param, grad, zero_grad, m, v, wt,
-                     ldt, R, C, lr, beta1, beta2, eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale, norm_sq,
-                     max_norm, step, base, seed);
+  hipLaunchKernelGGL((adamw_wt_kernel<MT, GUARD>), dim3(grid), dim3(256), 0, stream, master, param, grad, zero_grad,
+                     m, v, wt, ldt, R, C, lr, beta1, beta2, eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale,
+                     norm_sq, max_norm, step, base, seed, flag, skipped);
   return (int)hipGetLastError();
 }
 
@@ -467,6 +532,26 @@ extern "C" int toa_adamw_wt_bf16s(float* master, bf16_t* param, bf16_t* grad, in
                          step, grad_scale, norm_sq, max_norm, base, seed, stream);
 }
 
+// The GUARD arms (skipped steps, above): the same arguments, then flag and
+// skipped before the stream.
+extern "C" int toa_adamw_wt_guard(float* master, bf16_t* param, bf16_t* grad, int zero_grad, float* m, float* v,
+                                  bf16_t* wt, int64_t ldt, int R, int C, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int step, float grad_scale, const float* norm_sq,
+                                  float max_norm, const int* flag, const int* skipped, hipStream_t stream) {
+  return adamw_wt_launch<float, true>(master, param, grad, zero_grad, m, v, wt, ldt, R, C, lr, beta1, beta2, eps,
+                                      weight_decay, step, grad_scale, norm_sq, max_norm, 0, 0u, stream, flag, skipped);
+}
+
+extern "C" int toa_adamw_wt_bf16s_guard(float* master, bf16_t* param, bf16_t* grad, int zero_grad, bf16_t* m,
+                                        bf16_t* v, bf16_t* wt, int64_t ldt, int R, int C, float lr, float beta1,
+                                        float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                        const float* norm_sq, float max_norm, int64_t base, uint32_t seed,
+                                        const int* flag, const int* skipped, hipStream_t stream) {
+  return adamw_wt_launch<bf16_t, true>(master, param, grad, zero_grad, m, v, wt, ldt, R, C, lr, beta1, beta2, eps,
+                                       weight_decay, step, grad_scale, norm_sq, max_norm, base, seed, stream, flag,
+                                       skipped);
+}
+
 // Variant switch for in-process A/B (scripts/stream_ab.py,
 // scripts/adamw_grid_bench.py): bit 0 = the non-temporal AdamW, bit 1 = the
 // row-structured non-temporal SwiGLU, bits 8.. = AdamW grid cap / 1024 (0:
@@ -486,12 +571,13 @@ extern "C" int toa_set_stream_variant(int v) {
 
 // grad_flags: bit 0 = grad is bf16 (else fp32); bit 1 = zero the gradient
 // after reading it (the next step's zero_grad pass, fused).
-template <typename MT>
+template <typename MT, bool GUARD = false>
 static int adamw_launch(float* master, bf16_t* param, void* grad, int grad_flags, MT* m, MT* v, int64_t n,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                         const float* norm_sq, float max_norm, const int* step_dev, int64_t base, uint32_t seed,
-                        hipStream_t stream) {
+                        hipStream_t stream, const int* flag = nullptr, const int* skipped = nullptr) {
   if (n % 8 != 0) return (int)hipErrorInvalidValue;
+  if (GUARD && (flag == nullptr || skipped == nullptr || step < 1)) return (int)hipErrorInvalidValue;
   const int64_t n8 = n / 8;
   const float bc1 = 1.f - powf(beta1, (float)step);
   const float bc2 = 1.f - powf(beta2, (float)step);
@@ -503,11 +589,12 @@ static int adamw_launch(float* master, bf16_t* param, void* grad, int grad_flags
   // non-temporal only for sweeps far beyond the caches: a small model's whole
   // optimizer state (MNIST: 2.2 MB) stays L2-resident between graph replays; 8M+ parameters per launch
   const bool nt = (g_stream_variant & 1) && n8 >= (int64_t)(1 << 20);
-  auto k = (grad_flags & 1) ? (nt ? adamw_flat_kernel<true, true, MT> : adamw_flat_kernel<true, false, MT>)
-                            : (nt ? adamw_flat_kernel<false, true, MT> : adamw_flat_kernel<false, false, MT>);
+  auto k = (grad_flags & 1)
+               ? (nt ? adamw_flat_kernel<true, true, MT, GUARD> : adamw_flat_kernel<true, false, MT, GUARD>)
+               : (nt ? adamw_flat_kernel<false, true, MT, GUARD> : adamw_flat_kernel<false, false, MT, GUARD>);
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, stream, master, param, grad, zero_grad, m, v, n8, lr, beta1, beta2,
                      eps, weight_decay, inv_bc1, inv_sqrt_bc2, grad_scale, norm_sq, max_norm, step_dev, step, base,
-                     seed);
+                     seed, flag, skipped);
   return (int)hipGetLastError();
 }
 
@@ -536,6 +623,27 @@ extern "C" int toa_adamw_flat_bf16s(float* master, bf16_t* param, void* grad, in
   if (!bf16s_args_ok(master, param, grad, m, v, n, base) || step < 1) return (int)hipErrorInvalidValue;
   return adamw_launch(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                       norm_sq, max_norm, nullptr, base, seed, stream);
+}
+
+// The GUARD arms of the two host-step forms (skipped steps, above): the same
+// arguments, then flag and skipped before the stream.  The device-step forms
+// have none.
+extern "C" int toa_adamw_flat_guard(float* master, bf16_t* param, void* grad, int grad_flags, float* m, float* v,
+                                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                    int step, float grad_scale, const float* norm_sq, float max_norm, const int* flag,
+                                    const int* skipped, hipStream_t stream) {
+  return adamw_launch<float, true>(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay, step,
+                                   grad_scale, norm_sq, max_norm, nullptr, 0, 0u, stream, flag, skipped);
+}
+
+extern "C" int toa_adamw_flat_bf16s_guard(float* master, bf16_t* param, void* grad, int grad_flags, bf16_t* m,
+                                          bf16_t* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                          float weight_decay, int step, float grad_scale, const float* norm_sq,
+                                          float max_norm, int64_t base, uint32_t seed, const int* flag,
+                                          const int* skipped, hipStream_t stream) {
+  if (!bf16s_args_ok(master, param, grad, m, v, n, base) || step < 1) return (int)hipErrorInvalidValue;
+  return adamw_launch<bf16_t, true>(master, param, grad, grad_flags, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                                    step, grad_scale, norm_sq, max_norm, nullptr, base, seed, stream, flag, skipped);
 }
 
 // ... with the step (bias corrections AND rounding bits) read from

@@ -40,6 +40,12 @@ def main(argv=None):
                         "(default: TOA_ADAM_STATE, else fp32)")
     p.add_argument("--zero-check", action="store_true", default=None,
                    help="raise on a weight read whose ZeRO-1 all-gather was not waited for (default: TOA_ZERO_CHECK)")
+    p.add_argument("--skip-nonfinite", action="store_true", default=None,
+                   help="skip the update of a step whose gradient norm is Inf or NaN, on the device; the log "
+                        "line counts the skips (default: TOA_SKIP_NONFINITE)")
+    p.add_argument("--skip-grad-norm", type=float, default=None, metavar="X",
+                   help="with --skip-nonfinite: also skip a step whose gradient norm is above X "
+                        "(default: TOA_SKIP_GRAD_NORM, else no limit)")
     p.add_argument("--doc-mask", action="store_true",
                    help="pack rows from documents ending with --eos-id and keep attention inside each document")
     p.add_argument("--eos-id", type=int, default=0, help="the end-of-document token id of --doc-mask")
@@ -83,7 +89,8 @@ def _train(a, rt, info):
     dev = pick_device() if info.backend != "gloo" or os.environ.get("TOA_DIST_BACKEND") else torch.device("cpu")
     zero = rt.world > 1 if a.zero == "auto" else a.zero == "1"
     tr = LlamaTrainer(a.model, dev, micro_batch=a.micro_batch, seq_len=a.seq_len, lr=a.lr, shard_optimizer=zero,
-                      adam_state=a.adam_state, zero_check=a.zero_check, doc_eos=a.eos_id if a.doc_mask else None)
+                      adam_state=a.adam_state, zero_check=a.zero_check, doc_eos=a.eos_id if a.doc_mask else None,
+                      skip_nonfinite=a.skip_nonfinite, skip_grad_norm=a.skip_grad_norm)
     rt.mark("model_init")
     tr.on_phase = rt.mark  # the first step's host-side issue points, in the start-up phases
     ck = sharded_ckpt.Checkpointer(rt.ckpt_dir, rt.rank, rt.world) if rt.ckpt_dir else None
@@ -108,7 +115,9 @@ def _train(a, rt, info):
             rt.first_step_done()
             t1 = time.perf_counter()
         if tr.step_idx % 5 == 0 or tr.step_idx == a.steps:
-            rt.log(f"step {tr.step_idx} loss {float(loss):.4f}")
+            # float(loss) synchronises already, so the skip count costs no further wait
+            skipped = f" skipped {tr.skipped_steps()}" if tr.skip_nonfinite else ""
+            rt.log(f"step {tr.step_idx} loss {float(loss):.4f}{skipped}")
         if a.report_every and (tr.step_idx - n0) % a.report_every == 0 and tr.step_idx > n0 + 1:
             # throughput since the first step of this generation (excludes start-up)
             if dev.type == "cuda":

@@ -45,6 +45,17 @@ _SIGS = {
                                    c_i64, ctypes.c_uint32, c_p],
     "toa_adamw_wt_bf16s": [c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_int,
                            c_f, c_p, c_f, c_i64, ctypes.c_uint32, c_p],
+    # skipped steps: the verdict kernel (norm_sq, grad_scale, limit, flag, skipped, stream), and the update
+    # forms' arguments with flag and skipped before the stream
+    "toa_adamw_guard": [c_p, c_f, c_f, c_p, c_p, c_p],
+    "toa_adamw_flat_guard": [c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_p, c_f,
+                             c_p, c_p, c_p],
+    "toa_adamw_flat_bf16s_guard": [c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_p, c_f,
+                                   c_i64, ctypes.c_uint32, c_p, c_p, c_p],
+    "toa_adamw_wt_guard": [c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_int,
+                           c_f, c_p, c_f, c_p, c_p, c_p],
+    "toa_adamw_wt_bf16s_guard": [c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_f,
+                                 c_int, c_f, c_p, c_f, c_i64, ctypes.c_uint32, c_p, c_p, c_p],
     "toa_norm_set_fwd_cap": [c_int],
     "toa_lastline_arm": [ctypes.c_char_p, c_i64, c_i64, c_int],
     "toa_lastline_disarm": [],

@@ -117,6 +117,17 @@ def adamw_reference(master, grad, m, v, *, lr, beta1, beta2, eps, weight_decay, 
         v_out.copy_(vb)
 
 
+def check_skip_limit(skip_nonfinite: bool, skip_grad_norm) -> float:
+    """The skipped-step guard's norm limit (0 = none) as a float; ValueError
+    for a negative or non-finite one, and for a limit with the guard off."""
+    limit = float(skip_grad_norm or 0.0)
+    if not math.isfinite(limit) or limit < 0:
+        raise ValueError(f"skip_grad_norm must be a finite number >= 0, not {skip_grad_norm!r}")
+    if limit > 0 and not skip_nonfinite:
+        raise ValueError("skip_grad_norm needs skip_nonfinite: the limit is part of the skipped-step guard")
+    return limit
+
+
 _MASKED = []   # (ExternalStream, handle): kept for the process's life
 
 
@@ -165,13 +176,31 @@ class FlatAdamW:
     (sr_bf16_reference) with a counter hash of (seed, step, flat index), so
     they stay unbiased where round-to-nearest would stall (v at beta2 =
     0.999), and resume, sharded and W^T-writing updates stay bit-for-bit
-    (docs/kernels.md "bf16 moments")."""
+    (docs/kernels.md "bf16 moments").
+
+    skip_nonfinite=True: a step whose global gradient norm is Inf or NaN (or,
+    with skip_grad_norm > 0, above that limit after grad_scale) is skipped:
+    master, m, v, the bf16 weights and the W^T copies stay as they are on
+    every rank, and ``skipped_steps()`` counts it.  The verdict is one small
+    kernel after the norm (toa_adamw_guard) and the update kernels obey it,
+    so the step still never synchronises with the host.  Later steps take
+    their bias corrections and rounding draws from step - skipped, as if the
+    skipped step had never been taken.  The norm pass is paid even with
+    max_grad_norm = 0 (no clip is applied then).  Not with device_step.
+    (docs/kernels.md "Skipped steps")."""
 
     def __init__(self, flat, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1, max_grad_norm=1.0,
                  overlap=False, buckets=None, fuse_zero_grad=False, post_update=None, owned=None, group=None,
-                 device_step=False, state_dtype=torch.float32, seed=0):
+                 device_step=False, state_dtype=torch.float32, seed=0, skip_nonfinite=False, skip_grad_norm=0.0):
         if state_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"state_dtype must be torch.float32 or torch.bfloat16, not {state_dtype!r}")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.skip_grad_norm = check_skip_limit(self.skip_nonfinite, skip_grad_norm)
+        if self.skip_nonfinite and device_step:
+            raise ValueError("skip_nonfinite: the device-step (graph-replayed) update has no guarded form")
+        # flag: this step's verdict; skipped: the skipped steps so far (int32, on the device)
+        self._flag = torch.zeros(1, device=flat.device, dtype=torch.int32) if self.skip_nonfinite else None
+        self._skipped = torch.zeros(1, device=flat.device, dtype=torch.int32) if self.skip_nonfinite else None
         self.state_dtype = state_dtype
         self.seed = int(seed) & _U32
         self.post_update = post_update
@@ -248,6 +277,13 @@ class FlatAdamW:
     def _bf16_state(self) -> bool:
         return self.flat.exp_avg.dtype == torch.bfloat16
 
+    def _guarded(self, fn, tail, stream):
+        """The entry point and the arguments after max_norm: with the guard
+        on, the _guard form, which takes flag and skipped before the stream."""
+        if not self.skip_nonfinite:
+            return fn, (*tail, stream)
+        return fn + "_guard", (*tail, _lib.ptr(self._flag), _lib.ptr(self._skipped), stream)
+
     def _launch(self, a, b, decay, lr, grad_scale, clip, zero, stream):
         f = self.flat
         gflags = int(f.grad.dtype == torch.bfloat16) | (2 if zero else 0)
@@ -260,7 +296,8 @@ class FlatAdamW:
             raise ValueError(f"update run [{a}, {b}) crosses fp32 state ranges")
         es = f.exp_avg.element_size()
         # bf16 moments: the rounding bits are keyed by the FLAT index a, not the compact one
-        tail = (a, self.seed, stream) if bf else (stream,)
+        tail = (a, self.seed) if bf else ()
+        fn, tail = self._guarded(fn, tail, stream)
         _lib.call(fn, f.master.data_ptr() + 4 * si, pp, f.grad.data_ptr() + f.grad.element_size() * a,
                   gflags, f.exp_avg.data_ptr() + es * si, f.exp_avg_sq.data_ptr() + es * si, b - a, float(lr),
                   float(self.beta1), float(self.beta2), float(self.eps),
@@ -274,7 +311,8 @@ class FlatAdamW:
         wt = self.fused_wt
         f = self.flat
         if (wt is None or self.owned is not None or self.device_step or f.grad.dtype != torch.bfloat16
-                or not _lib.has("toa_adamw_wt_bf16s" if self._bf16_state() else "toa_adamw_wt")):
+                or not _lib.has(("toa_adamw_wt_bf16s" if self._bf16_state() else "toa_adamw_wt")
+                                + ("_guard" if self.skip_nonfinite else ""))):
             return {}
         out = {}
         for a, b, p, view in wt.items:
@@ -290,8 +328,8 @@ class FlatAdamW:
         R, C = p.shape
         bf = self._bf16_state()
         es = f.exp_avg.element_size()
-        tail = (a, self.seed, stream) if bf else (stream,)
-        _lib.call("toa_adamw_wt_bf16s" if bf else "toa_adamw_wt", f.master.data_ptr() + 4 * si,
+        fn, tail = self._guarded("toa_adamw_wt_bf16s" if bf else "toa_adamw_wt", (a, self.seed) if bf else (), stream)
+        _lib.call(fn, f.master.data_ptr() + 4 * si,
                   f.param.data_ptr() + 2 * a,
                   f.grad.data_ptr() + 2 * a, int(bool(self.fuse_zero_grad)), f.exp_avg.data_ptr() + es * si,
                   f.exp_avg_sq.data_ptr() + es * si, _lib.ptr(view), view.stride(0), R, C, float(lr),
@@ -330,6 +368,32 @@ class FlatAdamW:
         if dist.is_initialized():
             dist.all_reduce(self._norm, op=dist.ReduceOp.SUM, group=self.group)
 
+    def _verdict(self, grad_scale):
+        """flag = this step is skipped; skipped += flag (toa_adamw_guard, or
+        the same in host arithmetic for CPU tensors).  self._norm is final."""
+        if _lib.use_hip(self._norm):
+            _lib.call("toa_adamw_guard", _lib.ptr(self._norm), float(grad_scale), self.skip_grad_norm,
+                      _lib.ptr(self._flag), _lib.ptr(self._skipped), _lib.stream(self._norm))
+            return
+        ns = self._norm[0]
+        bad = not bool(torch.isfinite(ns))
+        if not bad and self.skip_grad_norm > 0:
+            bad = bool(ns.sqrt() * torch.tensor(grad_scale, dtype=torch.float32) > self.skip_grad_norm)
+        self._flag.fill_(int(bad))
+        self._skipped.add_(int(bad))
+
+    def _host_step(self) -> int:
+        """CPU path: the step the reference update takes its bias corrections
+        and rounding key from, step - skipped; 0 when this step is skipped."""
+        if not self.skip_nonfinite:
+            return self.step_count
+        return 0 if int(self._flag) else self.step_count - int(self._skipped)
+
+    def skipped_steps(self) -> int:
+        """Steps the guard skipped so far.  Synchronises with the device:
+        for logging points, not for every step."""
+        return int(self._skipped.item()) if self.skip_nonfinite else 0
+
     def wait_bucket(self, b):
         """Make the current stream wait until bucket b's parameters are updated."""
         if self.overlap and not self.waited[b]:
@@ -358,8 +422,11 @@ class FlatAdamW:
         self.step_count += 1
         lr = self.lr if lr is None else lr
         clip = self.max_grad_norm and self.max_grad_norm > 0
-        if clip:
+        if clip or self.skip_nonfinite:   # the guard needs the norm (final: all-reduced when sharded) too
             self._norm_sq()
+        if self.skip_nonfinite:
+            # the verdict, on the current stream: before the side stream's wait in overlap mode
+            self._verdict(grad_scale)
         if bucket_order is not None and self.owned is not None and not self.overlap:
             self._step_pipelined(lr, grad_scale, clip, bucket_order, after_bucket, before_bucket)
             return
@@ -383,8 +450,9 @@ class FlatAdamW:
             self.done = torch.cuda.Event()
             self.done.record(self.side)
             # tensors used on the side stream must not be recycled by the main stream's allocator
-            for t in (f.grad, f.param, f.master, f.exp_avg, f.exp_avg_sq, self._norm):
-                t.record_stream(self.side)
+            for t in (f.grad, f.param, f.master, f.exp_avg, f.exp_avg_sq, self._norm, self._flag, self._skipped):
+                if t is not None:
+                    t.record_stream(self.side)
             self.grads_zeroed = self.fuse_zero_grad
             return
         self.grads_zeroed = False
@@ -414,11 +482,12 @@ class FlatAdamW:
             elif self.post_update is not None:
                 self.post_update(0, f.numel)
         else:
-            for (a, b, decay) in self._work_runs():
+            st = self._host_step()
+            for (a, b, decay) in (self._work_runs() if st else ()):
                 adamw_reference(f.state_view(f.master, a, b), f.grad[a:b], f.state_view(f.exp_avg, a, b),
                                 f.state_view(f.exp_avg_sq, a, b), lr=lr,
                                 beta1=self.beta1, beta2=self.beta2, eps=self.eps,
-                                weight_decay=self.weight_decay if decay else 0.0, step=self.step_count,
+                                weight_decay=self.weight_decay if decay else 0.0, step=st,
                                 grad_scale=grad_scale, norm_sq=self._norm if clip else None,
                                 max_norm=self.max_grad_norm or 0.0, base=a, seed=self.seed)
             for lo, hi in (self.owned or [(0, f.numel)]):
@@ -432,6 +501,7 @@ class FlatAdamW:
         hip = _lib.use_hip(f.grad)
         if hip and self.device_step:
             _lib.call("toa_step_inc", _lib.ptr(self._dstep), _lib.stream(f.grad))
+        st = None if hip else self._host_step()   # 0: skipped -- the shards are gathered unchanged
         for b in order:
             lo, hi = self.owned[b]
             if before is not None:
@@ -442,11 +512,11 @@ class FlatAdamW:
                     continue
                 if hip:
                     self._launch(a2, b2, decay, lr, grad_scale, clip, self.fuse_zero_grad, _lib.stream(f.grad))
-                else:
+                elif st:
                     adamw_reference(f.state_view(f.master, a2, b2), f.grad[a2:b2], f.state_view(f.exp_avg, a2, b2),
                                     f.state_view(f.exp_avg_sq, a2, b2), lr=lr, beta1=self.beta1,
                                     beta2=self.beta2, eps=self.eps,
-                                    weight_decay=self.weight_decay if decay else 0.0, step=self.step_count,
+                                    weight_decay=self.weight_decay if decay else 0.0, step=st,
                                     grad_scale=grad_scale, norm_sq=self._norm if clip else None,
                                     max_norm=self.max_grad_norm or 0.0, base=a2, seed=self.seed)
             if not hip or f.param.dtype != torch.bfloat16:
@@ -461,15 +531,26 @@ class FlatAdamW:
         return self.step_count
 
     def state_dict(self):
-        return {"step": self.sync_step_count(), "lr": self.lr, "seed": self.seed,
-                "state_dtype": "bfloat16" if self.state_dtype == torch.bfloat16 else "float32"}
+        sd = {"step": self.sync_step_count(), "lr": self.lr, "seed": self.seed,
+              "state_dtype": "bfloat16" if self.state_dtype == torch.bfloat16 else "float32"}
+        if self.skip_nonfinite:   # only then: an unguarded run's state keeps its keys
+            sd["skipped"] = self.skipped_steps()
+        return sd
 
     def load_state_dict(self, sd):
         """The saved seed is adopted (a resumed run draws the uninterrupted
         run's rounding bits).  The saved moment dtype is informational: this
         optimizer keeps its own, and moments restored in the other one are
-        converted (FlatParams.load_state_shards, or here)."""
+        converted (FlatParams.load_state_shards, or here).  "skipped" (absent:
+        0) is restored with the guard on; an unguarded optimizer continues
+        from the step the updates had reached, step - skipped."""
         self.step_count = int(sd["step"])
+        skipped = int(sd.get("skipped", 0))
+        if self.skip_nonfinite:
+            self._skipped.fill_(skipped)
+            self._flag.zero_()
+        else:
+            self.step_count -= skipped
         if self.device_step:
             self._dstep.fill_(self.step_count)
         self.lr = sd.get("lr", self.lr)

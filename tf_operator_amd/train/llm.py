@@ -23,7 +23,7 @@ import torch
 
 from ..models.llama import PRESETS, Llama, LlamaConfig
 from ..ops.llm import doc_bounds
-from ..ops.optim import FlatAdamW
+from ..ops.optim import FlatAdamW, check_skip_limit
 from ..ops.wt import TransposedWeights, enabled_default
 from ..parallel.ddp import GradBucketer, broadcast_params
 from ..parallel import zero
@@ -36,9 +36,27 @@ class LlamaTrainer:
     def __init__(self, cfg: LlamaConfig | str, device, micro_batch=1, seq_len=4096, grad_accum=1, lr=3e-4,
                  seed=0, bucket_mb=None, overlap_optimizer=None, shard_optimizer=None,
                  transposed_weights=None, force_collectives=False, adam_state=None, zero_check=None,
-                 zero_poison=None, zero_ag_delay_us=None, doc_eos=None):
+                 zero_poison=None, zero_ag_delay_us=None, doc_eos=None, skip_nonfinite=None, skip_grad_norm=None):
         if isinstance(cfg, str):
             cfg = PRESETS[cfg]
+        # skip_nonfinite (None: TOA_SKIP_NONFINITE, default 0): a step whose global gradient norm is Inf or
+        # NaN -- or above skip_grad_norm (None: TOA_SKIP_GRAD_NORM, default 0 = no limit) -- leaves the
+        # weights, the optimizer state and the W^T copies untouched on every rank, decided and obeyed on
+        # the device (ops/optim.py FlatAdamW skip_nonfinite; docs/kernels.md "Skipped steps")
+        if skip_nonfinite is None:
+            env = os.environ.get("TOA_SKIP_NONFINITE", "0")
+            if env not in ("0", "1"):
+                raise ValueError(f"TOA_SKIP_NONFINITE must be 0 or 1, not {env!r}")
+            skip_nonfinite = env == "1"
+        if skip_grad_norm is None:
+            env = os.environ.get("TOA_SKIP_GRAD_NORM", "0")
+            try:
+                skip_grad_norm = float(env)
+            except ValueError:
+                raise ValueError(f"TOA_SKIP_GRAD_NORM must be a number, not {env!r}") from None
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.skip_grad_norm = check_skip_limit(self.skip_nonfinite, skip_grad_norm)
+        guard = dict(skip_nonfinite=self.skip_nonfinite, skip_grad_norm=self.skip_grad_norm)
         # doc_eos: a token id.  Each micro-batch's rows are then taken as documents that end with that
         # token, and attention stays inside each document (ops.llm.doc_bounds, the masked attention
         # kernels).  Targets are left as they are: the EOS position still predicts the next document's
@@ -103,7 +121,7 @@ class LlamaTrainer:
             # fp32 master / m / v only for the owned shards: 12 B/param x (1 - 1/world) of HBM freed
             self.flat.shard_state(self.bucketer.owned)
             self.bucketer.pull_rs = self._pull_reduce()
-            self.opt = FlatAdamW(self.flat, lr=lr, owned=self.bucketer.owned, state_dtype=state_dtype)
+            self.opt = FlatAdamW(self.flat, lr=lr, owned=self.bucketer.owned, state_dtype=state_dtype, **guard)
             self.gather = ParamGather(self.flat, self.bucketer.buckets, self.bucketer.rank, self.bucketer.world,
                                       on_gathered=self.wt.refresh if self.wt else None, emulator=self.bucketer.emu,
                                       pull=self._pull_gather(), check=self.zero_check, poison=self.zero_poison,
@@ -113,7 +131,7 @@ class LlamaTrainer:
                 overlap_optimizer = os.environ.get("TOA_OPT_OVERLAP", "0") == "1"
             self.opt = FlatAdamW(self.flat, lr=lr, overlap=overlap_optimizer, buckets=self.bucketer.buckets,
                                  fuse_zero_grad=not self.fresh_grads,
-                                 post_update=self.wt.refresh if self.wt else None, state_dtype=state_dtype)
+                                 post_update=self.wt.refresh if self.wt else None, state_dtype=state_dtype, **guard)
             if self.wt is not None and os.environ.get("TOA_ADAM_WT", "1") != "0":
                 # the update writes the W^T copies itself (ops/optim.py toa_adamw_wt)
                 self.opt.fused_wt = self.wt
@@ -145,7 +163,7 @@ class LlamaTrainer:
 
         if (os.environ.get("TOA_FUSED_NORM", "1") == "0" or self.flat.device.type != "cuda"
                 or not _lib.has("toa_wgrad_asm_set_sumsq") or self.gather is not None
-                or self.bucketer.world != 1 or not self.opt.max_grad_norm):
+                or self.bucketer.world != 1 or not (self.opt.max_grad_norm or self.opt.skip_nonfinite)):
             return
         head = model.head_weight()
         lin = [p for n, p in model.named_parameters() if p.dim() == 2 and not n.startswith("embed.")]
@@ -390,6 +408,11 @@ class LlamaTrainer:
         if emu is not None:
             lo, hi = self.gather.ranges[b]
             emu.fused_reduce(self.flat.grad[lo:hi])
+
+    def skipped_steps(self) -> int:
+        """Steps the skipped-step guard dropped so far (0 with the guard
+        off).  Synchronises with the device: for logging points."""
+        return self.opt.skipped_steps()
 
     def tokens_per_step(self, world=1):
         return self.micro_batch * self.seq_len * self.grad_accum * world

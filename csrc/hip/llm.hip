@@ -322,16 +322,20 @@ __global__ __launch_bounds__(512) void xent_fwd_kernel(const T* __restrict__ log
 #pragma unroll
     for (int j = 1; j < 8; ++j) mx = fmaxf(mx, f[j]);
     float mn = fmaxf(m, mx);
+    // everything so far -inf (a masked vocabulary): subtract 0, not -inf, so
+    // the terms are exp(-inf) = 0 and not exp(-inf + inf) = NaN (cf. lse_merge)
+    const float mr = mn == -INFINITY ? 0.f : mn;
     float acc = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc += __expf(f[j] - mn);
-    s = s * __expf(m - mn) + acc;
+    for (int j = 0; j < 8; ++j) acc += __expf(f[j] - mr);
+    s = s * __expf(m - mr) + acc;
     m = mn;
   }
   for (int i = v8 * 8 + threadIdx.x; i < V; i += blockDim.x) {
     float f = ld1<T>(x + i);
     float mn = fmaxf(m, f);
-    s = s * __expf(m - mn) + __expf(f - mn);
+    const float mr = mn == -INFINITY ? 0.f : mn;
+    s = s * __expf(m - mr) + __expf(f - mr);
     m = mn;
   }
   // wave reduce of (m, s)

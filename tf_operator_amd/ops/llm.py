@@ -256,7 +256,8 @@ class _CrossEntropy(torch.autograd.Function):
         t = target.reshape(-1).to(torch.int64).contiguous()
         rows = x.shape[0]
         if _lib.use_hip(x):
-            if x.stride(-1) != 1:
+            # rows may be strided (a column slice of a padded buffer); they must not overlap (an expanded row)
+            if x.stride(-1) != 1 or (rows > 1 and x.stride(0) < V):
                 x = x.contiguous()
             loss = torch.empty(rows, device=x.device, dtype=torch.float32)
             lse = torch.empty(rows, device=x.device, dtype=torch.float32)
@@ -280,7 +281,9 @@ class _CrossEntropy(torch.autograd.Function):
         x, t, lse, n_valid = ctx.saved_tensors
         V = x.shape[-1]
         if _lib.use_hip(x):
-            dx = x if ctx.inplace else torch.empty_like(x)
+            # the kernel writes dx with x's row stride: empty_like of a non-dense view would be dense (row
+            # stride V), and every row after the first would land in the wrong place or past the end
+            dx = x if ctx.inplace else torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
             go = g.reshape(1).float().contiguous()
             nv = n_valid.reshape(1).contiguous()
             _lib.call("toa_xent_bwd", _lib.dtype_code(x), _lib.ptr(x), _lib.ptr(t), _lib.ptr(lse), _lib.ptr(go),

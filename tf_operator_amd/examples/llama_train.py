@@ -9,6 +9,7 @@ which is what the elastic policy relies on."""
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import time
 
@@ -51,7 +52,16 @@ def main(argv=None):
     p.add_argument("--eos-id", type=int, default=0, help="the end-of-document token id of --doc-mask")
     p.add_argument("--doc-len", dest="doc_len_arg", default="16:128", metavar="LO:HI",
                    help="document lengths of the synthetic stream under --doc-mask")
+    p.add_argument("--sample-every", type=int, default=0, metavar="N",
+                   help="every N steps rank 0 samples greedily from the start of its current batch (KV-cache "
+                        "decoding) and prints one JSON line {\"sample\": {\"step\", \"tokens\"}}; 0 = never")
+    p.add_argument("--sample-tokens", type=int, default=16, metavar="M", help="new tokens per sample")
+    p.add_argument("--sample-prompt-len", type=int, default=8, metavar="P", help="prompt tokens per sample")
     a = p.parse_args(argv)
+    if a.sample_every < 0 or a.sample_tokens < 1 or a.sample_prompt_len < 1:
+        p.error("--sample-every needs N >= 0, --sample-tokens and --sample-prompt-len at least 1")
+    if a.sample_every and a.sample_prompt_len > a.seq_len:
+        p.error("--sample-prompt-len is longer than --seq-len")
     a.doc_len = None
     if a.doc_mask:
         try:
@@ -83,6 +93,16 @@ def _stop_agreed(rt, dev) -> bool:
     return bool(t.item() > 0)
 
 
+def _sample(a, tr, tokens):
+    """One greedy sample from the first --sample-prompt-len tokens of the
+    batch's first row, as one JSON line on stdout.  It leaves the run as it
+    was (LlamaTrainer.generate); the token list's copy to the host is the
+    only synchronisation."""
+    P = a.sample_prompt_len
+    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens)
+    print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
+
+
 def _train(a, rt, info):
     # gloo is the CPU plumbing backend, unless asked for explicitly
     # (TOA_DIST_BACKEND=gloo: replicas sharing one GPU, device tensors over gloo)
@@ -108,7 +128,10 @@ def _train(a, rt, info):
         rt.mark("checkpoint_load")
     t0, n0 = time.perf_counter(), tr.step_idx
     while tr.step_idx < a.steps:
-        loss = tr.step([data.next()])
+        batch = data.next()
+        loss = tr.step([batch])
+        if a.sample_every and tr.step_idx % a.sample_every == 0 and rt.rank == 0:
+            _sample(a, tr, batch[0])
         if tr.step_idx == n0 + 1:
             if dev.type == "cuda":
                 torch.cuda.synchronize()

@@ -24,9 +24,11 @@ import math
 
 import torch
 
+from ..ops.decode import KVCache, attn_decode, check_split_keys, rope_append
 from ..ops.embedding import Embedding
 from ..ops.linear import linear
-from ..ops.llm import (attention_block, cross_entropy, rope_cossin, rope_tables, swiglu_mlp, swiglu_mlp_resadd_ok)
+from ..ops.llm import (attention_block, causal_attention, cross_entropy, rope_cossin, rope_qkv, rope_tables, swiglu_mlp,
+                       swiglu_mlp_resadd_ok)
 from ..ops.norm import RMSNorm
 from ..parallel.zero_check import reading
 
@@ -183,3 +185,89 @@ class Llama(torch.nn.Module):
         if targets is None:
             return logits.view(B, S, -1)
         return cross_entropy(logits, targets.reshape(-1), inplace_grad=True)
+
+    # ---- KV-cache decoding (ops/decode.py; docs/kernels.md "Decoding").  Additions: forward is as it was.
+    def new_cache(self, batch, capacity, device=None, dtype=None):
+        """An empty KVCache of this model's layers, KV heads and head dim."""
+        w = self.embed.weight
+        return KVCache(self.cfg.layers, batch, self.cfg.kv_heads, capacity, self.cfg.head_dim,
+                       w.device if device is None else device, w.dtype if dtype is None else dtype)
+
+    def _check_cache(self, cache, B):
+        cfg = self.cfg
+        if (cache.layers, cache.kv_heads, cache.head_dim) != (cfg.layers, cfg.kv_heads, cfg.head_dim):
+            raise ValueError(f"KV cache of {cache.layers} layers x {cache.kv_heads} kv heads x head dim "
+                             f"{cache.head_dim} for a model of {cfg.layers} x {cfg.kv_heads} x {cfg.head_dim}")
+        if cache.batch != B:
+            raise ValueError(f"KV cache of {cache.batch} rows for a batch of {B}")
+
+    def _logits_of(self, h, delta, rows=None):
+        """Final norm and head of the residual stream h (+ delta); rows: an index into the tokens."""
+        _, x = self.norm(h, delta)
+        if rows is not None:
+            x = x[rows]
+        head = self.head_weight()
+        reading(head, "lm_head")
+        return linear(x, head)
+
+    @torch.no_grad()
+    def prefill(self, tokens, cache, lengths=None):
+        """Run the prompts tokens [B, P] (ragged ones right-padded; lengths:
+        host ints, default P each) through the training ops, copy every
+        layer's rotated K and V into the cache and return the logits [B, V] of
+        position lengths[b]-1.  Causality keeps the pads out of every valid
+        position, and cache slots at or beyond lengths[b] are never read."""
+        cfg = self.cfg
+        B, P = tokens.shape
+        self._check_cache(cache, B)
+        lengths = [P] * B if lengths is None else [int(n) for n in lengths]
+        if len(lengths) != B or min(lengths) < 1 or max(lengths) > P:
+            raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {B}")
+        if P > cache.capacity:
+            raise ValueError(f"KV cache overflow: a prompt of {P} tokens exceeds the capacity {cache.capacity}")
+        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        cos, sin, _ = self.rope(cache.capacity, tokens.device)
+        cos, sin = cos[:P], sin[:P]
+        h = self.embed(tokens).view(B * P, cfg.hidden)
+        delta = None
+        for i, blk in enumerate(self.blocks):
+            if delta is None:
+                x = blk.attn_norm(h)
+            else:
+                h, x = blk.attn_norm(h, delta)
+            q, k, v = rope_qkv(linear(x, blk.wqkv), cos, sin, B, P, Hq, Hkv, D, 1)
+            cache.k[i][:, :, :P] = k
+            cache.v[i][:, :, :P] = v
+            o = causal_attention(q, k, v, out_layout="bshd").reshape(B * P, Hq * D)
+            h, x = blk.mlp_norm(h, linear(o, blk.wo))
+            delta = swiglu_mlp(x, blk.wgu, blk.wd)
+        cache.set_lengths(lengths)
+        last = torch.tensor([b * P + n - 1 for b, n in enumerate(lengths)], device=tokens.device)
+        return self._logits_of(h, delta, last)
+
+    @torch.no_grad()
+    def decode_step(self, tokens, cache, split_keys=None):
+        """One new token per row, tokens [B], against the cache: appends the
+        token's rotated K and V at each row's length and returns the logits
+        [B, V] of that position.  No host synchronisation; past the cache's
+        capacity it raises ValueError before any launch."""
+        cfg = self.cfg
+        (B,) = tokens.shape
+        self._check_cache(cache, B)
+        split_keys = check_split_keys(split_keys)
+        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        cos, sin, _ = self.rope(cache.capacity, tokens.device)
+        cache.append()
+        pos, lens, max_len = cache.positions, cache.lengths, cache.max_len
+        h = self.embed(tokens)
+        delta = None
+        for i, blk in enumerate(self.blocks):
+            if delta is None:
+                x = blk.attn_norm(h)
+            else:
+                h, x = blk.attn_norm(h, delta)
+            q = rope_append(linear(x, blk.wqkv), cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D)
+            o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len)
+            h, x = blk.mlp_norm(h, linear(o.view(B, Hq * D), blk.wo))
+            delta = swiglu_mlp(x, blk.wgu, blk.wd)
+        return self._logits_of(h, delta)

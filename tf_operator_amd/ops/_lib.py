@@ -110,6 +110,10 @@ _SIGS = {
     "toa_attn_fwd_doc": [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p],
     "toa_attn_bwd_doc": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_f, c_p],
+    # decoding (csrc/hip/decode.hip): qkv cos sin pos q kcache vcache, B Hq Hkv D C table_rows;
+    # q kcache vcache len workspace o, B Hq Hkv C D max_len split_keys scale
+    "toa_decode_rope_append": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p],
+    "toa_attn_decode": [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p],
     "toa_wgrad": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],
     "toa_wgrad_split": [c_int, c_int, c_int],
     "toa_wgrad_asm": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],

@@ -1,0 +1,203 @@
+"""KV-cache decoding ops: the cache, RoPE + append of one token per row, and
+one query row per head against the cached keys.
+
+HIP kernels: csrc/hip/decode.hip (``toa_decode_rope_append``,
+``toa_attn_decode``: split over keys, fp32 partials, a merge kernel); CPU
+tensors take a plain PyTorch reference (fp32 math, the result in the tensor's
+dtype), row by row, so the CPU tier runs the whole feature.
+
+Cache layout: K and V are [B, Hkv, C, D] per layer, C the capacity, K stored
+rotated.  Row b attends slots 0 .. len[b]-1; slots at or beyond len[b] are
+never read into a result.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _lib
+
+HEAD_DIMS = (64, 128)     # the kernels' head-dim instantiations (csrc/hip/decode.hip)
+# keys per workgroup of toa_attn_decode.  Chosen for long caches: 4096 keys x 8 KV heads x 8 rows are 1024
+# workgroups (4 per CU) of 128 KB of K + V each at head_dim 128
+SPLIT_KEYS_DEFAULT = 256
+
+
+def check_split_keys(split_keys) -> int:
+    """split_keys (None: the default) as the launcher takes it: a power of two >= 64."""
+    s = SPLIT_KEYS_DEFAULT if split_keys is None else split_keys
+    if not isinstance(s, int) or isinstance(s, bool) or s < 64 or s & (s - 1):
+        raise ValueError(f"split_keys must be a power of two >= 64, not {split_keys!r}")
+    return s
+
+
+def _check_heads(Hq, Hkv, D):
+    if D not in HEAD_DIMS:
+        raise ValueError(f"head_dim {D} not in {HEAD_DIMS}")
+    if Hq < 1 or Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"query heads {Hq} not a multiple of kv heads {Hkv}")
+
+
+class KVCache:
+    """K and V of every layer, [batch, kv_heads, capacity, head_dim] each, and
+    the rows' lengths.  The lengths live on the host (they are known there:
+    the prompt lengths, plus one per step) and are mirrored on the device for
+    the kernels; ``append`` advances both without a synchronisation."""
+
+    def __init__(self, layers, batch, kv_heads, capacity, head_dim, device, dtype=torch.bfloat16):
+        if min(layers, batch, kv_heads, capacity) < 1:
+            raise ValueError(f"KVCache needs positive sizes (layers {layers}, batch {batch}, kv_heads {kv_heads}, "
+                             f"capacity {capacity})")
+        if head_dim not in HEAD_DIMS:
+            raise ValueError(f"head_dim {head_dim} not in {HEAD_DIMS}")
+        self.layers, self.batch, self.kv_heads, self.capacity, self.head_dim = layers, batch, kv_heads, capacity, head_dim
+        self.device, self.dtype = torch.device(device), dtype
+        shape = (batch, kv_heads, capacity, head_dim)
+        self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(layers)]
+        self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(layers)]
+        self.host_lengths = [0] * batch
+        # row 0: the last filled slot of each row (the position the newest token was appended at),
+        # row 1: the lengths.  One tensor, so one in-place add advances both.
+        self._state = torch.zeros(2, batch, device=device, dtype=torch.int32)
+        self._state[0] -= 1
+
+    @property
+    def positions(self):
+        """int32 [B] on the device: the slot of each row's newest token (len - 1)."""
+        return self._state[0]
+
+    @property
+    def lengths(self):
+        """int32 [B] on the device."""
+        return self._state[1]
+
+    @property
+    def max_len(self) -> int:
+        return max(self.host_lengths)
+
+    def set_lengths(self, lengths):
+        """The rows' lengths after a prefill (host ints); raises before anything is written."""
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != self.batch:
+            raise ValueError(f"{len(lengths)} lengths for a batch of {self.batch}")
+        if min(lengths) < 0 or max(lengths) > self.capacity:
+            raise ValueError(f"lengths {lengths} outside 0 .. capacity {self.capacity}")
+        self.host_lengths = lengths
+        n = torch.tensor(lengths, dtype=torch.int32)
+        self._state.copy_(torch.stack([n - 1, n]))
+
+    def append(self, n=1):
+        """Every row grows by n slots.  Past the capacity: ValueError, before
+        any launch and with nothing changed."""
+        if n < 1:
+            raise ValueError(f"append of {n} slots")
+        if self.max_len + n > self.capacity:
+            raise ValueError(f"KV cache overflow: length {self.max_len} + {n} exceeds the capacity {self.capacity}")
+        self.host_lengths = [x + n for x in self.host_lengths]
+        self._state += n
+
+
+def _check_cache(k_cache, v_cache, B, Hkv, D, like):
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dim() != 4 or t.shape[0] != B or t.shape[1] != Hkv or t.shape[3] != D:
+            raise ValueError(f"{name} {tuple(t.shape)} is not [B={B}, Hkv={Hkv}, C, D={D}]")
+        if t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous {like.dtype} on {like.device}")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} differ")
+
+
+def _check_rows(name, t, B, device):
+    if t.dtype != torch.int32 or tuple(t.shape) != (B,) or t.device != device:
+        raise ValueError(f"{name} must be an int32 [{B}] tensor on {device} (got {t.dtype} {tuple(t.shape)} on "
+                         f"{t.device})")
+    return t.contiguous()
+
+
+def rope_append(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv, D):
+    """One token per row: qkv [B, (Hq + 2 Hkv) D] (the fused projection's
+    output), cos / sin [rows, D/2] fp32 (ops.llm.rope_tables), pos int32 [B]
+    on the device.  Rotates q and k at position pos[b] with the convention
+    and the roundings of ops.llm.rope_qkv, returns q [B, Hq, D] and stores k
+    and v into slot pos[b] of the caches [B, Hkv, C, D]; no other slot is
+    written.  Positions are the caller's (KVCache.positions): a position
+    outside the cache or the table writes nothing on the GPU."""
+    _check_heads(Hq, Hkv, D)
+    B = qkv.shape[0]
+    if qkv.dim() != 2 or qkv.shape[1] != (Hq + 2 * Hkv) * D:
+        raise ValueError(f"qkv {tuple(qkv.shape)} is not [B, (Hq + 2 Hkv) D = {(Hq + 2 * Hkv) * D}]")
+    _check_cache(k_cache, v_cache, B, Hkv, D, qkv)
+    pos = _check_rows("pos", pos, B, qkv.device)
+    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.dtype != torch.float32:
+        raise ValueError(f"cos / sin {tuple(cos.shape)} {cos.dtype} are not fp32 [rows, D/2 = {D // 2}]")
+    C = k_cache.shape[2]
+    if _lib.use_hip(qkv):
+        if qkv.dtype != torch.bfloat16:
+            raise RuntimeError(f"HIP rope_append needs bf16 (got {qkv.dtype})")
+        qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
+        q = torch.empty(B, Hq, D, device=qkv.device, dtype=qkv.dtype)
+        _lib.call("toa_decode_rope_append", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(pos), _lib.ptr(q),
+                  _lib.ptr(k_cache), _lib.ptr(v_cache), B, Hq, Hkv, D, C, cos.shape[0], _lib.stream(qkv))
+        return q
+    p = pos.long()
+    x = qkv.view(B, Hq + 2 * Hkv, D)
+    d2 = D // 2
+    x1, x2 = x[:, :Hq + Hkv, :d2].float(), x[:, :Hq + Hkv, d2:].float()
+    c, s = cos[p][:, None], sin[p][:, None]
+    r = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(qkv.dtype)
+    rows = torch.arange(B)
+    k_cache[rows, :, p] = r[:, Hq:]
+    v_cache[rows, :, p] = x[:, Hq + Hkv:]
+    return r[:, :Hq].contiguous()
+
+
+def decode_ws_floats(B, Hq, D, max_len, split_keys) -> int:
+    """fp32 words of toa_attn_decode's workspace: per (row, head, split) D of
+    unnormalised output, the running maximum and the normaliser."""
+    return B * Hq * -(-max_len // split_keys) * (D + 2)
+
+
+def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_len=None):
+    """q [B, Hq, D] against the caches [B, Hkv, C, D]: row b attends keys
+    0 .. lengths[b]-1 (int32 [B] on the device); returns O [B, Hq, D].
+
+    On the GPU: toa_attn_decode, split_keys keys per workgroup (a power of
+    two >= 64; None: SPLIT_KEYS_DEFAULT) and a merge kernel.  max_len: a
+    host-side bound of the lengths (KVCache.max_len; None: the capacity) that
+    sizes the grid -- nothing is read back from the device.  A row's result
+    depends on that row's q, cache, length and split_keys only."""
+    split = check_split_keys(split_keys)
+    if q.dim() != 3:
+        raise ValueError(f"q {tuple(q.shape)} is not [B, Hq, D]")
+    B, Hq, D = q.shape
+    if k_cache.dim() != 4:
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} is not [B, Hkv, C, D]")
+    Hkv, C = k_cache.shape[1], k_cache.shape[2]
+    _check_heads(Hq, Hkv, D)
+    _check_cache(k_cache, v_cache, B, Hkv, D, q)
+    lengths = _check_rows("lengths", lengths, B, q.device)
+    max_len = C if max_len is None else int(max_len)
+    if not 1 <= max_len <= C:
+        raise ValueError(f"max_len {max_len} outside 1 .. capacity {C}")
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    if _lib.use_hip(q):
+        if q.dtype != torch.bfloat16:
+            raise RuntimeError(f"HIP attn_decode needs bf16 (got {q.dtype})")
+        q = q.contiguous()
+        ws = torch.empty(decode_ws_floats(B, Hq, D, max_len, split), device=q.device, dtype=torch.float32)
+        o = torch.empty_like(q)
+        _lib.call("toa_attn_decode", _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(lengths),
+                  _lib.ptr(ws), _lib.ptr(o), B, Hq, Hkv, C, D, max_len, split, scale, _lib.stream(q))
+        return o
+    rep = Hq // Hkv
+    out = torch.zeros(B, Hq, D, dtype=q.dtype)
+    for b, n in enumerate(lengths.tolist()):
+        n = min(n, max_len)
+        if n < 1:
+            continue
+        k = k_cache[b, :, :n].float().repeat_interleave(rep, 0)     # [Hq, n, D]
+        v = v_cache[b, :, :n].float().repeat_interleave(rep, 0)
+        s = torch.matmul(k, q[b].float()[:, :, None]).squeeze(-1) * scale
+        out[b] = torch.matmul(torch.softmax(s, -1)[:, None], v).squeeze(1).to(q.dtype)
+    return out

@@ -262,6 +262,26 @@ class LlamaTrainer:
         self.step_idx += 1
         return loss_sum / len(batches)
 
+    def generate(self, prompts, max_new_tokens, **kw):
+        """Sample from the current weights (train/generate.py: KV-cache
+        decoding; its keyword arguments).  Waits for the outstanding update
+        and every ZeRO-1 gather first, then runs under no_grad in eval mode.
+        The trainer's RNG states, gradients, optimizer state and step counter
+        are untouched (sampling draws from a generator of its own), so a run
+        with sampling between its steps is the run without it, bit for bit."""
+        from .generate import generate
+
+        self.opt.wait_all()
+        if self.gather is not None:
+            self.gather.wait_all()
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                return generate(self.model, prompts, max_new_tokens, **kw)
+        finally:
+            self.model.train(was_training)
+
     def _pull_gather(self):
         """TOA_ZERO_AG=sdma on a one-node GPU job (every rank on this node):
         the weight all-gather as copy-engine pulls (parallel/pull_gather.py)."""

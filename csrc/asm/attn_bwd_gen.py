@@ -127,33 +127,11 @@ V_X = 234                 # v234..v255 scratch (prologue / epilogue; in the loop
 # fragments a[128:159] / a[160:191] ([k-step] x 4)
 A_DV, A_DK, A_K, A_V = 0, 64, 128, 160
 
-# Schedule knobs; the DIAGNOSTIC arms (VARIANTS) switch one mechanism off to
-# price it in-process (scripts/attn_dkdv_arms.py): their outputs are wrong by
-# construction and only their time is read.
-KNOBS = {"bar": True, "vmwait": True, "lgkm": True, "exp": True, "dma": True, "valu": True, "lds": True,
-         "timing": False, "merge": True, "pk": False, "dsst": True, "dswide": False,
-         "gbar": G_BAR, "dldma": DL_DMA, "lead": 3}   # schedule parameters (the s* arms sweep them)
-VARIANTS = (
-    ("d1", {"lgkm": False}),                     # MFMAs do not wait for their LDS fragments
-    ("d2", {"bar": False, "vmwait": False}),     # no per-iteration barrier nor DMA wait
-    ("d3", {"exp": False}),                      # v_exp_f32 -> v_mov_b32
-    ("d4", {"dma": False, "vmwait": False}),     # no Q / dO staging in the loop
-    ("d5", {"valu": False}),                     # no softmax / dS VALU (stores kept)
-    ("d6", {"lds": False, "lgkm": False}),       # no LDS fragment reads
-    ("d7", {"lds": False, "lgkm": False, "valu": False, "dma": False, "vmwait": False, "bar": False}),  # MFMAs + SALU
-    ("t1", {"timing": True}),                    # the product kernel + s_memtime stamps (same outputs)
-    # schedule-parameter arms (correct outputs; A/B by time)
-    ("s1", {"gbar": 6}),
-    ("s2", {"gbar": 14}),
-    ("s3", {"dldma": 28}),
-    ("s4", {"lead": 2}),
-    ("s5", {"lead": 5}),
-    ("s6", {"merge": False}),
-    ("s7", {"pk": True}),                        # round 5: P / dS on packed v_pk_fma / v_pk_mul pairs
-    ("d8", {"dsst": False}),                     # DIAGNOSTIC: no dS block stores (the dQ GEMM's input)
-    ("s8", {"dswide": True}),                    # 16-B dS stores by permlane32 swaps (2 per block): measured
-                                                 # 0.8 % slower than the four 8-B ones (profiles/r6_dkdv/arms3.log)
-)
+# `timing`: the diagnostic arm t1 (VARIANTS), the product kernel + s_memtime
+# stamps (same outputs; toa_attn_dkdv_asm_timing).
+KNOBS = {"timing": False}
+VARIANTS = (("t1", {"timing": True}),)
+LEAD = 3                 # a fragment read's deadline: this many MFMAs ahead of the one that needs it
 
 MASK_C = AG.MASK_C        # register r's row offset in a 32x32 accumulator: (r & 3) + 8 (r >> 2)
 
@@ -282,26 +260,18 @@ def e_items(p: int, masked: bool, rel: int, dl: int, stream: str, st_rel: int | 
     S0, P0, L0 = sbuf(p), dpbuf(p), V_L + 16 * p
     if masked:
         items.append(Item([f"v_add_u32 {vr(V_MD)}, {sr(S_DD0 if p == 0 else S_DD1)}, {vr(V_MD0)}"], 4, rel, dl, stream))
-    pk = KNOBS["pk"]
     for j0 in range(0, 16, 4):
-        if pk:
-            ins = [f"v_pk_fma_f32 {vr(S0 + j, 2)}, {vr(S0 + j, 2)}, {vr(V_C2, 2)}, {vr(L0 + j, 2)}"
-                   for j in range(j0, j0 + 4, 2)]
-        else:   # scalar: beside MFMAs a packed f32 op costs more than two scalar ones (MI355X_MICROARCH.md
-                # 'price of one filler'; -3.5 % per call at the bench shape, profiles/r6_dkdv)
-            ins = [f"v_fma_f32 {vr(S0 + j)}, {vr(S0 + j)}, {vr(V_C2)}, {vr(L0 + j)}" for j in range(j0, j0 + 4)]
-        ins += [f"v_exp_f32 {vr(S0 + j)}, {vr(S0 + j)}" if KNOBS["exp"] else f"v_mov_b32 {vr(S0 + j)}, {vr(S0 + j)}"
-                for j in range(j0, j0 + 4)]
+        # scalar ops: beside MFMAs a packed f32 op costs more than two scalar ones (MI355X_MICROARCH.md
+        # 'price of one filler'; -3.5 % per call at the bench shape, profiles/r6_dkdv)
+        ins = [f"v_fma_f32 {vr(S0 + j)}, {vr(S0 + j)}, {vr(V_C2)}, {vr(L0 + j)}" for j in range(j0, j0 + 4)]
+        ins += [f"v_exp_f32 {vr(S0 + j)}, {vr(S0 + j)}" for j in range(j0, j0 + 4)]
         items.append(Item(ins, 0, rel, dl, stream))
         if masked:   # key > query -> 0; each vcc pair kept together
             for j in range(j0, j0 + 4):
                 items.append(Item([f"v_cmp_lt_i32 vcc, {MASK_C[j]}, {vr(V_MD)}",
                                    f"v_cndmask_b32 {vr(S0 + j)}, {vr(S0 + j)}, 0, vcc"], 8, rel, dl, stream, split=False))
         ins = [f"v_cvt_pk_bf16_f32 {vr(V_PW + 8 * p + j // 2)}, {vr(S0 + j)}, {vr(S0 + j + 1)}" for j in range(j0, j0 + 4, 2)]
-        if pk:
-            ins += [f"v_pk_mul_f32 {vr(P0 + j, 2)}, {vr(S0 + j, 2)}, {vr(P0 + j, 2)}" for j in range(j0, j0 + 4, 2)]
-        else:
-            ins += [f"v_mul_f32 {vr(P0 + j)}, {vr(S0 + j)}, {vr(P0 + j)}" for j in range(j0, j0 + 4)]
+        ins += [f"v_mul_f32 {vr(P0 + j)}, {vr(S0 + j)}, {vr(P0 + j)}" for j in range(j0, j0 + 4)]
         ins += [f"v_cvt_pk_bf16_f32 {vr(V_SW + 8 * p + j // 2)}, {vr(P0 + j)}, {vr(P0 + j + 1)}" for j in range(j0, j0 + 4, 2)]
         items.append(Item(ins, 0, rel, dl, stream))
     # dS block store: the lane's 4 queries 8 g + 4 hh .. + 3 of key r are the
@@ -310,38 +280,9 @@ def e_items(p: int, masked: bool, rel: int, dl: int, stream: str, st_rel: int | 
     srd = SRD_DS0 if p == 0 else SRD_DS1
     dso = S_DSO0 if p == 0 else S_DSO1
     srel = rel if st_rel is None else max(rel, st_rel)
-    nst = 0
-    if KNOBS["dswide"]:
-        # 16-B stores: the packs of groups 2k and 2k + 1 copied to scratch
-        # (the packs themselves are KV(n)'s B operands) and one
-        # v_permlane32_swap per dword, so lanes < 32 hold the 8 queries of
-        # group 2k and lanes >= 32 those of group 2k + 1 for their key (the
-        # lane offset V_DSO then steps 512 B per lane half): 2 stores per
-        # block instead of 4.  The stores cost 14 % of the kernel (arm d8),
-        # but not through their count: this arm (s8) is 0.8 % slower than the
-        # product's four 8-B stores (profiles/r6_dkdv/arms3.log).  The movs of
-        # both pairs go first, so a swap reads scratch written >= 3
-        # instructions earlier.
-        tmp = [V_X + 8 * p + 4 * k for k in range(2)]
-        for k in range(2):
-            items.append(Item([f"v_mov_b32 {vr(tmp[k] + e)}, {vr(V_SW + 8 * p + 4 * k + e)}" for e in range(4)], 0,
-                              max(srel, rel + 1), max(srel, dl), stream))
-        for k in range(2):
-            items.append(Item([f"v_permlane32_swap_b32 {vr(tmp[k])}, {vr(tmp[k] + 2)}",
-                               f"v_permlane32_swap_b32 {vr(tmp[k] + 1)}, {vr(tmp[k] + 3)}",
-                               f"buffer_store_dwordx4 {vr(tmp[k], 4)}, {vr(V_DSO)}, {sr(srd, 4)}, {sr(dso)} "
-                               f"offen offset:{1024 * k} nt"], 16, max(srel, rel + 1), max(srel, dl), stream,
-                              split=False))
-        nst = 4
-    else:
-        for g in range(4):
-            items.append(Item([f"buffer_store_dwordx2 {vr(V_SW + 8 * p + 2 * g, 2)}, {vr(V_DSO)}, {sr(srd, 4)}, "
-                               f"{sr(dso)} offen offset:{512 * g} nt"], 8, max(srel, rel + 1), max(srel, dl), stream))
-        nst = 4
-    if not KNOBS["dsst"]:   # DIAGNOSTIC: no dS block stores
-        items = items[:-nst]
-    if not KNOBS["valu"]:
-        items = items[-nst:] if KNOBS["dsst"] else []
+    for g in range(4):
+        items.append(Item([f"buffer_store_dwordx2 {vr(V_SW + 8 * p + 2 * g, 2)}, {vr(V_DSO)}, {sr(srd, 4)}, "
+                           f"{sr(dso)} offen offset:{512 * g} nt"], 8, max(srel, rel + 1), max(srel, dl), stream))
     for it in items:
         if it.cost == 0:
             it.cost = sum(AG.issue_cost(x) for x in it.ins)
@@ -439,7 +380,7 @@ def kv_read_items(base: int, m: int, buf: int, base_prev: int | None, pre: bool,
     items = []
     for i in range(NPRE if pre else 0, 16):
         rel = slot_rel(i, base, base_prev)
-        items.append(Item(kv_frag(i, m, buf), 8, rel, max(rel, base + i - KNOBS["lead"]), stream))
+        items.append(Item(kv_frag(i, m, buf), 8, rel, max(rel, base + i - LEAD), stream))
     return items
 
 
@@ -459,33 +400,17 @@ def sd_read_items(base: int, m: int, p: int, buf: int, rel0: int, base_prev: int
              Item(lr[:4], 16, ld_rel, max(ld_rel, base + 11), stream + "l")]
     for i in range(16):
         rel = max(rel0, slot_rel(i, base, base_prev))
-        items.append(Item([sd_frag(i, m, buf)], 4, rel, max(rel, base + i - KNOBS["lead"]), stream))
+        items.append(Item([sd_frag(i, m, buf)], 4, rel, max(rel, base + i - LEAD), stream))
     return items
 
 
-def schedule_merged(a: Asm, mfmas: list, items: list, tail=None, pre=()):
+def sched(a: Asm, mfmas: list, items: list, tail=None, pre=()):
     """attn_gen.schedule, with each lgkmcnt wait also covering the next
     MFMA's fragments when they are already in flight (one wait per two
     MFMAs: each wait costs an issue slot, and one wave per SIMD issues at
     most one instruction per 4 cycles)."""
-    if not KNOBS["merge"]:
-        return schedule(a, mfmas, items, tail, pre=pre)
-    out = []
-
-    class Cap:          # collect schedule()'s output, then rewrite its waits
-        def __call__(self, txt):
-            out.append(txt)
-    saved = dict(AG.KNOBS)
-    AG.KNOBS["lgkm"] = False
-    try:
-        schedule(Cap(), mfmas, items, tail, pre=())
-    finally:
-        AG.KNOBS.clear()
-        AG.KNOBS.update(saved)
-    if not KNOBS["lgkm"]:
-        for t in out:
-            a(t)
-        return
+    out: list[str] = []   # schedule()'s output without waits; the replay below places them
+    schedule(out.append, mfmas, items, tail, waits=False)
     # replay: lds = tags of issued reads in order; before MFMA g wait for
     # the tags of g (and of g + 1 when all of them were read already)
     lds: list = list(pre)
@@ -518,23 +443,12 @@ def schedule_merged(a: Asm, mfmas: list, items: list, tail=None, pre=()):
             lds.append(t.split(";")[1].strip() if ";" in t else None)
 
 
-def sched(a: Asm, mf: list, items: list, tail=None, pre=()):
-    """The list schedule with this kernel's knobs (lgkm waits, LDS reads)."""
-    items = [it for it in items if it.ins]
-    if not KNOBS["lds"]:
-        items = [it for it in items if not it.ins[0].startswith("ds_read")]
-        mf = [(t, []) for t, _ in mf]
-        pre = ()
-    schedule_merged(a, mf, items, tail, pre=pre)
-
-
 # ---------------------------------------------------------------- loop bodies
 def iteration(a: Asm, m1: bool, m2: bool, ph: int, nxt: str):
     """One step it (not the last), it % 3 == ph: MFMAs KV(2 it) [0..15],
     SD(2 it + 2) [16..31], KV(2 it + 1) [32..47], SD(2 it + 3) [48..63].
     Tile it sits in buffer ph, tile it + 1 in ph + 1, tile it + 2 goes to ph + 2."""
     kbuf, sbuf_, dbuf = ph, (ph + 1) % 3, (ph + 2) % 3
-    G_BAR, DL_DMA = KNOBS["gbar"], KNOBS["dldma"]   # noqa: N806 -- the sweep arms' values
     mf = kv_mfmas(0) + sd_mfmas(0) + kv_mfmas(1) + sd_mfmas(1)
     n = len(mf)
     items: list[Item] = []
@@ -542,11 +456,9 @@ def iteration(a: Asm, m1: bool, m2: bool, ph: int, nxt: str):
     items += kv_read_items(0, 0, kbuf, None, True, "kr")
     items += kv_read_items(32, 1, kbuf, 0, False, "kr2")
     # the barrier: every wave's pieces of tile it + 1 landed (vmcnt: only the
-    # dS stores of E(2 it) -- issued after every DMA piece, two 16-B or four
-    # 8-B ones -- and any since may be outstanding), every wave done with tile it - 1
-    vm = 2 if KNOBS["dswide"] else 4
-    items.append(Item(([f"s_waitcnt vmcnt({vm})"] if KNOBS["vmwait"] else []) + (["s_barrier"] if KNOBS["bar"] else []),
-                      8, G_BAR, G_BAR, "bar", split=False))
+    # four dS stores of E(2 it) -- issued after every DMA piece -- and any
+    # since may be outstanding), every wave done with tile it - 1
+    items.append(Item(["s_waitcnt vmcnt(4)", "s_barrier"], 8, G_BAR, G_BAR, "bar", split=False))
     # SD reads (tile it + 1): SD(2 it + 2) after the barrier; SD(2 it + 3)'s
     # -lse / -delta rows after E(2 it + 1) let go of the parity-1 registers
     items += sd_read_items(16, 0, 0, sbuf_, G_BAR, None, G_BAR, "sr")
@@ -558,7 +470,7 @@ def iteration(a: Asm, m1: bool, m2: bool, ph: int, nxt: str):
     items += e_items(0, m2, 33, 61, "e2", st_rel=DL_DMA + 1)
     # DMA of tile min(it + 2, last) into buffer ph + 2, after the barrier
     items.append(Item(dma_setup(), 16, -1, G_BAR, "dma", split=False))
-    for ins in dma_pieces(dbuf) if KNOBS["dma"] else []:
+    for ins in dma_pieces(dbuf):
         items.append(Item(ins, 48, G_BAR, DL_DMA, "dma", split=False))
     # bookkeeping for the next iteration, and KV(2 it + 2)'s first fragments
     # (tile it + 1; their ring slots last used by MFMAs 44, 45)
@@ -761,9 +673,8 @@ def prologue(a: Asm):
     a(f"v_mov_b32 {vr(V_C2 + 1)}, {sr(S_C)}")
     # dS store: key 16 + hh 8; mask base r - 4 hh
     a(f"v_lshlrev_b32 {vr(V_DSO)}, 4, {vr(r)}")
-    # lane half hh: + 8 B (4 of the group's 8 queries) for the 8-B stores, + 512 B
-    # (the next query group) for the 16-B ones (e_items)
-    a(f"v_lshl_add_u32 {vr(V_DSO)}, {vr(hh)}, {9 if KNOBS['dswide'] else 3}, {vr(V_DSO)}")
+    # lane half hh: + 8 B (4 of the group's 8 queries; e_items' 8-B stores)
+    a(f"v_lshl_add_u32 {vr(V_DSO)}, {vr(hh)}, 3, {vr(V_DSO)}")
     a(f"v_lshlrev_b32 {vr(t)}, 2, {vr(hh)}")
     a(f"v_sub_u32 {vr(V_MD0)}, {vr(r)}, {vr(t)}")
     # --- K / V rows of this wave's keys -> B-operand fragments (AGPRs)
@@ -1012,7 +923,7 @@ def variant_kernel(vname: str, knobs: dict) -> tuple[str, str]:
 
 
 def all_kernels() -> list[tuple[str, str]]:
-    """The product kernel, then the diagnostic arms (host table order)."""
+    """The product kernel, then its timing arm."""
     return [kernel()] + [variant_kernel(v, k) for v, k in VARIANTS]
 
 

@@ -106,20 +106,10 @@ V_SB = (112, 176)         # score buffers (64 each): [block][key half] x 16
 V_X = 240                 # v240..v255 scratch (row max, rescale, epilogue)
 RING = 6
 
-# Schedule knobs; the DIAGNOSTIC arms (VARIANTS) switch one mechanism off to
-# price it in-process (scripts/attn_fwd_ab.py --variants): their outputs are
-# wrong by construction and only their time is read.
-KNOBS = {"bar": True, "vmwait": True, "lgkm": True, "exp": True, "dma": True, "timing": False, "fine": True}
-VARIANTS = (
-    ("d1", {"bar": False, "vmwait": False}),   # no per-tile barrier nor DMA wait
-    ("d2", {"vmwait": False}),                 # barrier, but not for the DMA to land
-    ("d3", {"lgkm": False}),                   # MFMAs do not wait for their LDS fragments
-    ("d4", {"exp": False}),                    # v_exp_f32 -> v_mov_b32 (transcendental issue cost)
-    ("d5", {"dma": False, "vmwait": False}),   # no K / V staging in the loop
-    ("t1", {"timing": True}),                  # the product kernel + s_memtime stamps (bit-identical outputs)
-    ("c1", {"fine": False}),                   # fillers placed as whole groups (the first schedule)
-    ("t2", {"timing": True, "fine": False}),   # its timing arm
-)
+# `timing`: the diagnostic arm t1 (VARIANTS), the product kernel + s_memtime
+# stamps (bit-identical outputs; toa_attn_fwd_asm_timing).
+KNOBS = {"timing": False}
+VARIANTS = (("t1", {"timing": True}),)
 
 # AGPRs: O^T a[0:127] ([block][d tile] x 16), Q^T fragments a[128:191]
 # ([block][k-step] x 4), row sums a[192:223] ([block] x 16)
@@ -216,19 +206,20 @@ def issue_cost(ins: str) -> int:
 GAP_BUDGET = 24     # filler issue cycles one 32x32x16 MFMA gap hides
 
 
-def schedule(a: Asm, mfmas: list, items: list, tail: list | None = None, pre=()):
+def schedule(a, mfmas: list, items: list, tail: list | None = None, pre=(), waits: bool = True):
     """Emit MFMAs (text, needed LDS tags) with the items spread over the gaps:
     earliest deadline first, against an even cumulative issue-cost line.
     LDS reads are tagged by a trailing "; tag" comment in their text; before
     an MFMA the lgkmcnt wait its tags need is inserted (LDS completes in
     order, so older outstanding reads do not change the count).  `pre`: tags
     read before this schedule (the previous loop body's prefetch), taken as
-    the most recent LDS ops at its start."""
+    the most recent LDS ops at its start.  waits=False: no lgkmcnt waits (the
+    caller places its own: attn_bwd_gen.schedule_merged)."""
     n = len(mfmas)
     streams: dict = {}
     for it in items:
         assert -1 <= it.rel <= n - 1 and it.dl >= it.rel, (it.ins[:1], it.rel, it.dl)
-        if it.split and KNOBS["fine"]:
+        if it.split:
             for ins in it.ins:
                 streams.setdefault(it.stream, []).append(Item([ins], issue_cost(ins), it.rel, it.dl, it.stream))
         else:
@@ -266,7 +257,7 @@ def schedule(a: Asm, mfmas: list, items: list, tail: list | None = None, pre=())
             lds.append(txt.split(";")[1].strip() if ";" in txt else None)
 
     def wait_for(tags):
-        if not KNOBS["lgkm"]:
+        if not waits:
             return
         need = 0
         for t in tags:
@@ -352,7 +343,7 @@ def exp_items(buf: int, base: int, stream="exp") -> list[Item]:
                 regs = [sreg(buf, qb2, kh, r0 + e) for e in range(4)]
                 p = preg(qb2, ks) + 2 * part
                 ins = [f"v_fma_f32 {vr(x)}, {vr(x)}, {sr(S_C)}, -{vr(V_M + qb2)}" for x in regs]
-                ins += [f"v_exp_f32 {vr(x)}, {vr(x)}" if KNOBS["exp"] else f"v_mov_b32 {vr(x)}, {vr(x)}" for x in regs]
+                ins += [f"v_exp_f32 {vr(x)}, {vr(x)}" for x in regs]
                 ins += [f"v_cvt_pk_bf16_f32 {vr(p)}, {vr(regs[0])}, {vr(regs[1])}",
                         f"v_cvt_pk_bf16_f32 {vr(p + 1)}, {vr(regs[2])}, {vr(regs[3])}"]
                 items.append(Item(ins, 58, -1, dl, stream))
@@ -456,7 +447,7 @@ def body(a: Asm, kind: str, p: int, resc_label: str, back_label: str):
              f"s_add_u32 {sr(S_T0)}, {sr(S_I)}, 1",
              f"s_lshl_b32 {sr(S_VT)}, {sr(S_T0)}, 14"]
     items.append(Item(setup, 10, -1, DL_DMA, "dma"))
-    for j in range(4 if KNOBS["dma"] else 0):
+    for j in range(4):
         items.append(Item(dma_piece("K", j, p), 40, -1, DL_DMA, "dma"))
         items.append(Item(dma_piece("V", j, p), 40, -1, DL_DMA, "dma"))
     items.append(Item([f"s_add_u32 {sr(S_M0V)}, {sr(S_M0V)}, {TILE}",
@@ -465,8 +456,7 @@ def body(a: Asm, kind: str, p: int, resc_label: str, back_label: str):
                        f"s_sub_u32 {sr(S_M0V)}, {sr(S_M0V)}, {sr(S_T0 + 1)}"], 8, -1, n - 1, "dma"))
     # --- the barrier: everyone's K_{i+2} / V_{i+1} landed; then the next
     # tile's K offsets and its first fragments
-    items.append(Item((["s_waitcnt vmcnt(0)"] if KNOBS["vmwait"] else []) + (["s_barrier"] if KNOBS["bar"] else []),
-                      8, G_BAR, G_BAR, "bar", split=False))
+    items.append(Item(["s_waitcnt vmcnt(0)", "s_barrier"], 8, G_BAR, G_BAR, "bar", split=False))
     items.append(Item(koff_toggle(), 32, G_BAR, n - 1, "bar"))
     for f in range(3):
         items.append(Item([kread(f)], 6, G_BAR, n - 1, "bar"))
@@ -508,7 +498,6 @@ def body(a: Asm, kind: str, p: int, resc_label: str, back_label: str):
             items.append(Item(mask_ins(q, qb2, 1, range(8, 16)), 64, rel1, n - 1, st))
         items.append(Item(b_ops, 4 * len(b_ops), rel1, n - 1, st))
         items.append(Item(max_final(qb2), 30, rel1, n - 1, st))
-    items = [it for it in items if it.ins]
     tail = [f"s_add_u32 {sr(S_I)}, {sr(S_I)}, 1",
             f"s_or_b64 {sr(S_F, 2)}, {sr(S_FA, 2)}, {sr(S_FB, 2)}",      # SCC: some row's max grew past THR
             f"s_cbranch_scc1 {resc_label}"]
@@ -895,7 +884,7 @@ def variant_kernel(vname: str, knobs: dict) -> tuple[str, str]:
 
 
 def all_kernels() -> list[tuple[str, str]]:
-    """The product kernel, then the diagnostic arms (host table order)."""
+    """The product kernel, then its timing arm."""
     return [kernel()] + [variant_kernel(v, k) for v, k in VARIANTS]
 
 

@@ -119,9 +119,6 @@ S_Q, S_R = 69, 70   # division results
 # barrier, W-free barrier), s88..s89 the kernel's start stamp
 S_TMT, S_ACC, S_T_START = 72, 84, 88
 S_ITER, S_GRID = 90, 91   # persistent arms: this workgroup's tile-order index, the grid size
-# deferred-store arm (SCHED "defer", never with the timing kernel, whose stamps
-# use s72..s89): the previous tile's C resource, its row-block offset and step
-SRD_D, S_DOFF, S_DSTEP = 72, 76, 77
 S_MAP, S_KGRID = 92, 93   # kernarg map / grid words (s94, s95: the map's decoded log2 group, walk flag)
 S_LG, S_WALK = 94, 95
 S_ADVW = 78         # NN kernels: 64 rows of W in bytes (the window's step per k-tile)
@@ -386,9 +383,6 @@ def tile_rows_bytes(a: Asm, dst: int, ld: int):
 def tile_c(a: Asm, epi: str):
     """SRD_C (and SRD_S) of the tile at (S_TM, S_TN)."""
     # C (and S): rows tm*256, columns tn*256 (tn*128 for the gate|up epilogue)
-    if SCHED["store_same"]:   # DIAGNOSTIC arm: every workgroup stores tile (0, 0)
-        a(f"s_mov_b32 {sr(S_TM)}, 0")
-        a(f"s_mov_b32 {sr(S_TN)}, 0")
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TM)}, 8")
     mul64(a, S_T2, S_T3, S_T0, S_LDC)
     a(f"s_lshl_b32 {sr(S_T0)}, {sr(S_TN)}, {8 if epi == 'swiglu_fwd' else 9}")  # column bytes
@@ -487,8 +481,6 @@ def prologue_lanes(a: Asm, epi: str):
     a(f"v_xor_b32 {vr(V_RXT)}, {vr(V_RXT)}, {vr(V_RX)}")
     a(f"v_add_u32 {vr(V_RWT)}, {STAGE}, {vr(V_RW)}")
     a(f"v_xor_b32 {vr(V_RWT)}, {vr(V_RWT)}, {vr(V_RW)}")
-    if not SCHED["zero_late"]:
-        zero_acc(a)
 
 
 def zero_acc(a: Asm):
@@ -526,28 +518,17 @@ def frag_read(kind: str, f: int, sub: int) -> str:
     return f"ds_read_b128 {vr(dst + 4 * f, 4)}, {vr(base)} offset:{off}"
 
 
-def mfma(i: int, j: int, sub: int, czero: bool = False) -> str:
-    """czero: the accumulator starts at 0 (srcC = inline 0: the tile's first
-    k-step, no zeroing pass)."""
+def mfma(i: int, j: int, sub: int) -> str:
     fw = (V_FW0 if sub == 0 else V_FW1) + 4 * i
     fx = (V_FX0 if sub == 0 else V_FX1) + 4 * j
     acc = 4 * (8 * i + j)
-    return f"v_mfma_f32_16x16x32_bf16 {ar(acc, 4)}, {vr(fw, 4)}, {vr(fx, 4)}, {'0' if czero else ar(acc, 4)}"
+    return f"v_mfma_f32_16x16x32_bf16 {ar(acc, 4)}, {vr(fw, 4)}, {vr(fx, 4)}, {ar(acc, 4)}"
 
 
-# schedule knobs of the main loop (A/B arms: PLAIN_VARIANTS)
-SCHED = {"dma_gap": 4, "prio": False, "wait_slot": 95, "read_gap": 1, "group": 4, "sub1_gap": 1, "xbar": 23,
-         "xdma_gap": 3, "merge_bar": False, "timing": 0,
-         "align": True, "drain_end": False, "map": "lib0", "persist": False, "dual": "", "zero_late": True,
-         "nostore": False, "store_nt": True, "store_same": False, "epi_pipe": True,
-         "epi_pk": True, "epi_f32s": True,
-         # DIAGNOSTIC arms of the SwiGLU backward epilogue (SWIGLU_BWD_VARIANTS;
-         # wrong outputs by design): no gu loads (ds stands in for gate and up),
-         # no SwiGLU math (the loaded gu stored as dgu), no dgu stores, no epilogue
-         "epi_noload": False, "epi_novalu": False, "epi_nostore": False, "epi_none": False,
-         # persistent plain kernel whose C stores are issued in the NEXT tile's
-         # first k-iteration (packed bf16 parked in a[128:255]; deferred_pack)
-         "defer": False}
+# What a kernel variant changes in the code below (_with_knobs): `persist`, a
+# workgroup per CU walks its tiles (PLAIN_VARIANTS, SWIGLU_PERSIST_VARIANTS);
+# `timing`, the diagnostic s_memtime stamps (1: waits, 2: stretches).
+SCHED = {"persist": False, "timing": 0}
 
 
 def _stamp(k: int) -> str:
@@ -561,140 +542,24 @@ def _accum(acc: int, k_end: int, k_begin: int) -> list[str]:
             f"s_add_u32 {sr(S_ACC + acc)}, {sr(S_ACC + acc)}, {sr(S_E0)}"]
 
 
-def iteration(a: Asm, with_dma: bool, next_reads: bool, vm_after_dma: int, trace_base: int = 0):
-    """One 64-k tile: 128 MFMAs with the reads / DMA / waits placed in the
-    gaps after MFMA n (n = 0..127; 0..63 phase 1, 64..127 phase 2)."""
-    gap = SCHED["dma_gap"]
-    slots: dict[int, list[str]] = {n: [] for n in range(128)}
-    # phase 1: sub-step 1 fragment reads of this stage (X then W)
-    g1 = SCHED["sub1_gap"]
-    w0 = 17 if g1 == 2 else 8 * g1
-    for j in range(8):
-        slots[g1 * j].append(frag_read("x", j, 1))
-    xb = SCHED["xbar"]
-    assert xb > g1 * 7
-    tm = SCHED["timing"] == 1      # waits: vmcnt / X-free / W-free barriers
-    sp = SCHED["timing"] == 2      # spans: X-DMA, W-DMA and bare MFMA stretches
-    if with_dma:
-        slots[xb] += ([_stamp(2)] if tm else []) + ["s_waitcnt lgkmcnt(0)", "s_barrier"] + ([_stamp(3)] if tm else [])
-    for i in range(8):
-        slots[w0 + g1 * i].append(frag_read("w", i, 1))
-    if with_dma and SCHED["merge_bar"]:
-        # one barrier frees both halves (every sub-step 1 read is issued
-        # before it), then the 16 DMA pieces, X first
-        assert w0 + g1 * 7 < xb
-        xg = SCHED["xdma_gap"]
-        for j in range(16):
-            slots[xb + 1 + xg * j] += dma(a, "x" if j < 8 else "w", j % 8)
-        assert xb + 1 + xg * 15 < 78
-        slots[xb + 1 + xg * 8 - 1] += advance("x")
-    elif with_dma:
-        xg = SCHED["xdma_gap"]
-        assert xb + 1 + xg * 7 < 47 and w0 + g1 * 7 < 47
-        for j in range(8):
-            slots[xb + 1 + xg * j] += dma(a, "x", j)
-        slots[47] += advance("x")
-        slots[47] += ([_stamp(4)] if tm else []) + ["s_waitcnt lgkmcnt(0)", "s_barrier"] + ([_stamp(5)] if tm else [])
-        for j in range(8):
-            slots[48 + gap * j] += dma(a, "w", j)               # 48..76
-    if with_dma:
-        slots[78] += advance("w")
-        slots[78] += [f"s_xor_b32 {sr(S_M0X)}, {sr(S_M0X)}, {sr(S_M0XT)}",
-                      f"s_xor_b32 {sr(S_M0W)}, {sr(S_M0W)}, {sr(S_M0WT)}"]
-        if trace_base:
-            slots[47] += trace_mark(trace_base + 1)
-            slots[78] += trace_mark(trace_base + 2)
-    if next_reads:
-        # the next tile (staged one iteration ago) has landed: own DMA by the
-        # counted wait, everyone's by the barrier
-        ws, rg = SCHED["wait_slot"], SCHED["read_gap"]
-        slots[ws] += ([_stamp(0)] if tm else []) + [f"s_waitcnt vmcnt({vm_after_dma})", "s_barrier"] + ([_stamp(1)] if tm else []) + [
-                      f"v_xor_b32 {vr(V_RX)}, {vr(V_RX)}, {vr(V_RXT)}",
-                      f"v_xor_b32 {vr(V_RW)}, {vr(V_RW)}, {vr(V_RWT)}"]
-        for j in range(8):
-            slots[ws + 1 + rg * j].append(frag_read("x", j, 0))
-        for i in range(8):
-            slots[ws + 1 + rg * (8 + i)].append(frag_read("w", i, 0))
-        assert ws + 1 + rg * 15 < 126
-        slots[126].append("s_waitcnt lgkmcnt(0)")
-        if tm:
-            slots[126] += _accum(0, 1, 0)
-        if sp and with_dma:
-            slots[126] += _accum(0, 1, 0) + _accum(1, 3, 2) + _accum(2, 5, 4)
-        if trace_base:
-            slots[ws] += trace_mark(trace_base + 3)
-    if sp and with_dma:
-        # stamps AFTER MFMA n (slot lists run after it): [24, 45] X DMA,
-        # [47 after the W barrier, 76] W DMA, [77, 94] bare MFMAs
-        assert not SCHED["merge_bar"] and xb == 23 and SCHED["xdma_gap"] == 3 and gap == 4 and ws == 95
-        slots[23].append(_stamp(0))
-        slots[45].append(_stamp(1))
-        slots[47].append(_stamp(2))
-        slots[76].append(_stamp(3))
-        slots[77].append(_stamp(4))
-        slots[94].append(_stamp(5))
-    if trace_base:
-        slots[127] += trace_mark(trace_base + 4)
-    if SCHED["prio"]:
-        slots[127].append("s_setprio 0")
-    for n in range(128):
-        sub, m = divmod(n, 64)
-        i, j = divmod(m, 8)
-        if n == 0 and SCHED["prio"]:
-            a("s_setprio 1")
-        if n == 64:
-            # phase 2 consumes the sub-step 1 fragments read in phase 1
-            a("s_waitcnt lgkmcnt(0)")
-            if tm and with_dma:
-                for ins in _accum(1, 3, 2) + ([] if SCHED["merge_bar"] else _accum(2, 5, 4)):
-                    a(ins)
-        if SCHED["align"]:
-            # every MFMA (8 B) on an 8-byte boundary: a hand-written stream
-            # shifted by 4 mod 8 bytes runs ~13 % slower on gfx950
-            # (MI355X_MICROARCH.md, code-placement sensitivity); the
-            # assembler pads with a 4-byte s_nop 0 only where needed
-            a(".p2alignl 3, 0xbf800000")
-        a(mfma(i, j, sub))
-        for ins in slots[n]:
-            a(ins)
-
-
-# Explicit slot maps (SCHED["map"]): every fragment read, barrier, DMA piece
-# and the next-tile wait placed after a given MFMA (0..127).  M0 is set once
-# before the first piece of each half and advanced right AFTER each piece, so
-# the next piece (at least one MFMA later) needs no s_nop.  The next-tile wait
+# The main loop's slot map: every fragment read, barrier, DMA piece and the
+# next-tile wait placed after a given MFMA (0..127), the placement a
+# well-tuned 4-wave, 256 x 256 x 64 library kernel uses on gfx950 (observed
+# from its instruction stream: pieces spread over the whole iteration, three
+# of the W pieces after the next-tile wait).  `split`: every barrier that
+# many MFMAs after its wait (the MFMA issued in between runs while the wave
+# waits at the barrier); `m0_lag`: M0, set once before the first piece of
+# each half, advances that many MFMAs after each piece, so the next piece (at
+# least one MFMA later) needs no s_nop; `adv`: the slots of the X / W resource
+# advances, a few MFMAs after the half's last piece.  The next-tile wait
 # counts the pieces issued before it in this iteration; pieces after it (for
-# tile t + 2) land by the NEXT iteration's wait.
-SLOT_MAPS = {
-    # the placement a well-tuned 4-wave, 256 x 256 x 64 library kernel uses
-    # on gfx950 (observed from its instruction stream: pieces spread over the
-    # whole iteration, three of the W pieces after the next-tile wait)
-    "spread": {"x1": [0, 2, 4, 6, 8, 10, 12, 14], "xbar": 20, "w1": [24, 27, 30, 33, 36, 38, 40, 42], "wbar": 50,
-               "xdma": [22, 25, 28, 31, 34, 52, 55, 58], "wdma": [61, 64, 85, 87, 89, 96, 100, 124], "wait": 91,
-               "x0": [93, 94, 95, 97, 98, 102, 103, 104], "w0": [105, 106, 109, 112, 114, 117, 120, 123]},
-    # the same, pieces evenly every 5-6 MFMAs
-    "spread2": {"x1": [0, 2, 4, 6, 8, 10, 12, 14], "xbar": 20, "w1": [24, 27, 30, 33, 36, 38, 40, 42],
-                "wbar": 50, "xdma": [22, 27, 32, 37, 42, 47, 52, 57], "wdma": [62, 68, 74, 80, 86, 98, 110, 122],
-                "wait": 91, "x0": [93, 94, 95, 97, 99, 101, 103, 104], "w0": [105, 106, 109, 112, 114, 117, 120, 123]},
-    # fewer pieces before the wait (10): a longer flight for the rest
-    "spread3": {"x1": [0, 2, 4, 6, 8, 10, 12, 14], "xbar": 20, "w1": [24, 27, 30, 33, 36, 38, 40, 42],
-                "wbar": 50, "xdma": [22, 26, 30, 34, 38, 44, 52, 58], "wdma": [64, 76, 93, 99, 105, 111, 117, 123],
-                "wait": 91, "x0": [94, 95, 96, 97, 98, 100, 101, 102], "w0": [103, 104, 106, 108, 110, 113, 116, 119]},
-    # "spread" as the library's main 256 x 256 kernel actually issues it:
-    # every barrier one MFMA after its wait, M0 advanced one MFMA after each
-    # piece, the resource advances a few MFMAs after the last piece
-    "lib0": {"x1": [0, 2, 4, 6, 8, 10, 12, 14], "xbar": 20, "w1": [24, 27, 30, 33, 36, 38, 40, 42], "wbar": 50,
-             "xdma": [22, 25, 28, 31, 34, 52, 55, 58], "wdma": [61, 64, 85, 87, 89, 96, 100, 124], "wait": 91,
-             "x0": [93, 94, 95, 97, 98, 102, 103, 104], "w0": [105, 106, 109, 112, 114, 117, 120, 123],
-             "split": 1, "m0_lag": 1, "adv": {"x": 65, "w": 125}},
-    # its partner for the waves on odd SIMDs (the library selects one of two
-    # loop bodies by the SIMD id): X pieces and W reads one MFMA apart from
-    # lib0's, the last four W pieces non-temporal
-    "lib1": {"x1": [0, 2, 4, 6, 8, 10, 12, 14], "xbar": 20, "w1": [22, 25, 28, 31, 34, 38, 40, 42], "wbar": 50,
-             "xdma": [23, 26, 29, 32, 35, 53, 56, 59], "wdma": [62, 65, 84, 86, 88, 95, 99, 123], "wait": 91,
-             "x0": [93, 94, 96, 97, 98, 102, 103, 104], "w0": [105, 106, 109, 112, 114, 117, 120, 122],
-             "split": 1, "m0_lag": 1, "adv": {"x": 66, "w": 125}, "nt_w": [4, 5, 6, 7]},
-}
+# tile t + 2) land by the NEXT iteration's wait.  Shared with the
+# weight-gradient kernel (wgrad_gen.iteration) and the NN kernels
+# (iteration_nn).
+SLOT_MAP = {"x1": [0, 2, 4, 6, 8, 10, 12, 14], "xbar": 20, "w1": [24, 27, 30, 33, 36, 38, 40, 42], "wbar": 50,
+            "xdma": [22, 25, 28, 31, 34, 52, 55, 58], "wdma": [61, 64, 85, 87, 89, 96, 100, 124], "wait": 91,
+            "x0": [93, 94, 95, 97, 98, 102, 103, 104], "w0": [105, 106, 109, 112, 114, 117, 120, 123],
+            "split": 1, "m0_lag": 1, "adv": {"x": 65, "w": 125}}
 
 
 def span_slots(m: dict):
@@ -711,21 +576,11 @@ def span_mfmas(m: dict) -> list[int]:
     return [hi - lo for lo, hi in span_slots(m)]
 
 
-def iteration_map(a: Asm, with_dma: bool, next_reads: bool, vm_after_dma: int, trace_base: int = 0,
-                  mapname: str = "", first: bool = False, extra: dict | None = None):
-    """One 64-k tile placed by an explicit slot map (SLOT_MAPS).  Map keys
-    beyond the placements: `split` puts each barrier that many MFMAs after
-    its wait (the MFMA issued in between runs while the wave waits at the
-    barrier); `m0_lag` advances M0 that many MFMAs after each piece instead
-    of right behind it; `adv` gives the slots of the X / W resource advances
-    (default: with the last piece of the half); `nt_w` the W pieces loaded
-    non-temporal.  first: the tile's first k-tile (phase-1 MFMAs start their
-    accumulators at 0); extra: {slot: [instructions]} placed after those
-    MFMAs (the deferred C stores: their VMEM ops before the next-tile wait
-    are counted in its vmcnt)."""
-    m = SLOT_MAPS[mapname or SCHED["map"]]
-    split, lag = m.get("split", 0), m.get("m0_lag", 0)
-    nt_w = set(m.get("nt_w", ()))
+def iteration_map(a: Asm, with_dma: bool, next_reads: bool):
+    """One 64-k tile placed by SLOT_MAP: 128 MFMAs (0..63 sub-step 0, 64..127
+    sub-step 1) with the reads / DMA / waits in the gaps after them."""
+    m = SLOT_MAP
+    split, lag = m["split"], m["m0_lag"]
     slots: dict[int, list[str]] = {n: [] for n in range(128)}
     for j, n in enumerate(m["x1"]):
         slots[n].append(frag_read("x", j, 1))
@@ -733,6 +588,7 @@ def iteration_map(a: Asm, with_dma: bool, next_reads: bool, vm_after_dma: int, t
         slots[n].append(frag_read("w", i, 1))
     assert max(m["x1"]) < m["xbar"] and max(m["w1"]) < m["wbar"] and max(m["x1"] + m["w1"]) < 63
     tm, sp = SCHED["timing"] == 1, SCHED["timing"] == 2
+    vm = 0
     if with_dma:
         for bar in (m["xbar"], m["wbar"]):
             slots[bar].append("s_waitcnt lgkmcnt(0)")
@@ -744,26 +600,19 @@ def iteration_map(a: Asm, with_dma: bool, next_reads: bool, vm_after_dma: int, t
             slots[pos[0] - 1].append(f"s_mov_b32 m0, {sr(m0)}")
             for j, n in enumerate(pos):
                 soff = "0" if j == 0 else sr(so + j - 1)
-                nt = " nt" if half == "w" and j in nt_w else ""
-                slots[n].append(f"buffer_load_dwordx4 {vr(vo)}, {sr(srd_, 4)}, {soff} offen{nt} lds")
+                slots[n].append(f"buffer_load_dwordx4 {vr(vo)}, {sr(srd_, 4)}, {soff} offen lds")
                 if j < 7:
                     # an MFMA between every M0 write and the next piece (the
                     # M0 -> LDS-DMA hazard wants one wait state)
                     assert pos[j + 1] > n + lag
                     slots[n + lag].append(f"s_add_u32 m0, m0, {4 * LINE}")
-            adv = m.get("adv", {}).get(half, pos[-1])
-            assert adv >= pos[-1]
+            adv = m["adv"][half]
+            assert pos[-1] <= adv < 128
             slots[adv] += advance(half) + [f"s_xor_b32 {sr(m0)}, {sr(m0)}, {sr(m0 + 1)}"]
         # the two halves' pieces must not interleave (one running M0)
         assert max(m["xdma"]) + lag < min(m["wdma"]) - 1
-        assert m.get("adv", {}).get("x", 0) < 128 and m.get("adv", {}).get("w", 0) < 128
         vm = sum(1 for n in m["xdma"] + m["wdma"] if n < m["wait"])
-    else:
-        vm = 0
-    for n, ins in (extra or {}).items():
-        slots[n] += ins
-        if n < m["wait"] or (n == m["wait"] and not next_reads):
-            vm += sum(1 for x in ins if x.startswith(("buffer_", "global_")))
+
     def stamp_around(k, n):
         """stamp k before the wait in slot n, stamp k+1 right after its
         barrier (slot n + split; with a split the MFMA between them counts)"""
@@ -775,161 +624,41 @@ def iteration_map(a: Asm, with_dma: bool, next_reads: bool, vm_after_dma: int, t
         for k, bar in ((2, m["xbar"]), (4, m["wbar"])):
             stamp_around(k, bar)
     if with_dma and sp:  # stretches: X pieces, W pieces before the wait, W pieces after it
-        (x0, x1), (w0, w1), (v0, v1) = span_slots(m)
-        for k, (lo, hi) in enumerate(((x0, x1), (w0, w1), (v0, v1))):
+        for k, (lo, hi) in enumerate(span_slots(m)):
             slots[lo].append(_stamp(2 * k))
             slots[hi].append(_stamp(2 * k + 1))
     if next_reads:
+        # the next tile (staged one iteration ago) has landed: own DMA by the
+        # counted wait, everyone's by the barrier
         w = m["wait"]
-        wait = [f"s_waitcnt vmcnt({vm if with_dma else vm_after_dma})"]
-        toggles = [f"v_xor_b32 {vr(V_RX)}, {vr(V_RX)}, {vr(V_RXT)}",
-                   f"v_xor_b32 {vr(V_RW)}, {vr(V_RW)}, {vr(V_RWT)}"]
-        slots[w] += wait
-        slots[w + split] += ["s_barrier"] + toggles
-        assert min(m["x0"] + m["w0"]) > w + split
+        slots[w].append(f"s_waitcnt vmcnt({vm})")
+        slots[w + split] += ["s_barrier", f"v_xor_b32 {vr(V_RX)}, {vr(V_RX)}, {vr(V_RXT)}",
+                             f"v_xor_b32 {vr(V_RW)}, {vr(V_RW)}, {vr(V_RWT)}"]
         if tm and with_dma:
             stamp_around(0, w)
-        assert min(m["x0"] + m["w0"]) > w and max(m["x0"] + m["w0"]) < 126
+        assert min(m["x0"] + m["w0"]) > w + split and max(m["x0"] + m["w0"]) < 126
         for j, n in enumerate(m["x0"]):
             slots[n].append(frag_read("x", j, 0))
         for i, n in enumerate(m["w0"]):
             slots[n].append(frag_read("w", i, 0))
         slots[126].append("s_waitcnt lgkmcnt(0)")
-        if with_dma and tm:
-            slots[126] += _accum(0, 1, 0) + _accum(1, 3, 2) + _accum(2, 5, 4)
-        if with_dma and sp:
+        if with_dma and (tm or sp):
             slots[126] += _accum(0, 1, 0) + _accum(1, 3, 2) + _accum(2, 5, 4)
     for n in range(128):
         sub, mm = divmod(n, 64)
         i, j = divmod(mm, 8)
         if n == 64:
+            # phase 2 consumes the sub-step 1 fragments read in phase 1
             a("s_waitcnt lgkmcnt(0)")
-        if SCHED["align"]:
-            a(".p2alignl 3, 0xbf800000")
-        a(mfma(i, j, sub, czero=first and sub == 0))
+        # every MFMA (8 B) on an 8-byte boundary: a hand-written stream
+        # shifted by 4 mod 8 bytes runs ~13 % slower on gfx950
+        # (MI355X_MICROARCH.md, code-placement sensitivity); the
+        # assembler pads with a 4-byte s_nop 0 only where needed
+        a(".p2alignl 3, 0xbf800000")
+        a(mfma(i, j, sub))
         for ins in slots[n]:
             a(ins)
 
-
-# ---------------------------------------------------------------- deferred C stores
-DEFER_AGPR = 128          # a[128:255]: the previous tile's C, packed bf16 (32 stores x 4 registers)
-
-
-def deferred_pack(a: Asm):
-    """The finished tile's accumulators -> bf16 pairs parked in a[128:255],
-    store k = 4 j + p (row block j, column pair p) in a[128 + 4k : +3]: the
-    data of epilogue_plain's store (j, p).  Staged through V4..V131 (the
-    fragment registers, free between tiles) because the packs overwrite
-    accumulators later row blocks still read."""
-    f = V_E + 8                                       # 32 fp32 of one row block
-    for j in range(8):
-        for p in range(4):
-            read_pair(a, f + 8 * p, p, j)
-        for p in range(4):
-            cvt_pack8(a, V_FX0 + 16 * j + 4 * p, f + 8 * p)
-    for r in range(128):
-        a(f"v_accvgpr_write_b32 {ar(DEFER_AGPR + r)}, {vr(V_FX0 + r)}")
-
-
-def deferred_stores() -> dict:
-    """{slot: instructions} of the previous tile's 32 C stores, store k after
-    MFMA k of the next tile's first k-tile: before MFMA 32 + k, whose
-    accumulator (fresh, srcC = 0) is the store's data register.  Row block j
-    at S_DOFF (advanced by 16 rows after its 4th store); a resource with
-    num_records 0 (the first tile: nothing deferred) drops them all."""
-    nt = " nt" if SCHED["store_nt"] else ""
-    out = {}
-    for k in range(32):
-        p = k % 4
-        ins = [f"buffer_store_dwordx4 {ar(DEFER_AGPR + 4 * k, 4)}, {vr(V_E)}, {sr(SRD_D, 4)}, {sr(S_DOFF)} offen "
-               f"offset:{64 * p}{nt}"]
-        if p == 3:
-            ins.append(f"s_add_u32 {sr(S_DOFF)}, {sr(S_DOFF)}, {sr(S_DSTEP)}")
-        out[k] = ins
-    return out
-
-
-def kernel_defer(name: str) -> tuple[str, str]:
-    """The persistent plain kernel with deferred C stores (SCHED "defer"):
-    a workgroup per CU walks its tiles; tile t's C leaves as 32 stores spread
-    over tile t + 1's first k-iteration (one per MFMA gap, under the matrix
-    core's work) instead of a burst with the MFMA pipe idle at the end of
-    every tile -- the epilogue's HBM traffic costs the plain kernel 1-5 %
-    (the no-store arm, profiles/r6_nostore).  The next tile's first two
-    k-tiles are staged before the pack, so their flight hides under it;
-    its first k-step starts the accumulators at 0 (no zeroing pass)."""
-    a = Asm(prefix="defer_")
-    a.raw(f".globl {name}")
-    a.raw(".p2align 8")
-    a.raw(f".type {name},@function")
-    a.raw(f"{name}:")
-    prologue(a, "plain")
-    a(f"s_cmp_lt_u32 {sr(S_KT)}, 3")                # the first k-iteration is peeled: K >= 192
-    a(f"s_cbranch_scc1 {a.abort}")
-    epi_offsets(a, "plain")                          # V_E: this lane's C offset, the same in every tile
-    a(f"s_lshl_b32 {sr(S_DSTEP)}, {sr(S_LDC)}, 4")  # 16 rows
-    for r in range(4):                               # nothing deferred yet: num_records 0 drops the stores
-        a(f"s_mov_b32 {sr(SRD_D + r)}, {0x20000 if r == 3 else 0}")
-    prologue_dma(a)
-    a("s_waitcnt vmcnt(16)")
-    a("s_barrier")
-    l_tile, l_loop, l_tail, l_last = a.fresh("tile"), a.fresh("loop"), a.fresh("tail"), a.fresh("last")
-    a.label(l_tile)
-    for j in range(8):
-        a(frag_read("x", j, 0))
-    for i in range(8):
-        a(frag_read("w", i, 0))
-    a("s_waitcnt lgkmcnt(0)")
-    a(f"s_mov_b32 {sr(S_DOFF)}, 0")
-    iteration_map(a, with_dma=True, next_reads=True, vm_after_dma=16, first=True, extra=deferred_stores())
-    a(f"s_sub_u32 {sr(S_LOOP)}, {sr(S_KT)}, 3")
-    a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
-    a(f"s_cbranch_scc1 {l_tail}")
-    if SCHED["align"]:
-        a(".p2alignl 6, 0xbf800000")
-    a.label(l_loop)
-    iteration_map(a, with_dma=True, next_reads=True, vm_after_dma=16)
-    a(f"s_sub_u32 {sr(S_LOOP)}, {sr(S_LOOP)}, 1")
-    a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
-    a(f"s_cbranch_scc0 {l_loop}")
-    a.label(l_tail)
-    iteration_map(a, with_dma=False, next_reads=True, vm_after_dma=0)
-    iteration_map(a, with_dma=False, next_reads=False, vm_after_dma=0)
-    a("s_nop 15")                                    # MFMA results -> VALU reads
-    a("s_nop 15")
-    # --- next tile: stage parity back to 0 (M0 bases toggled KT times, read bases KT - 1)
-    l_even, l_par = a.fresh("even"), a.fresh("par")
-    a(f"s_bitcmp1_b32 {sr(S_KT)}, 0")
-    a(f"s_cbranch_scc0 {l_even}")
-    a(f"s_xor_b32 {sr(S_M0X)}, {sr(S_M0X)}, {sr(S_M0XT)}")
-    a(f"s_xor_b32 {sr(S_M0W)}, {sr(S_M0W)}, {sr(S_M0WT)}")
-    a(f"s_branch {l_par}")
-    a.label(l_even)
-    a(f"v_xor_b32 {vr(V_RX)}, {vr(V_RX)}, {vr(V_RXT)}")
-    a(f"v_xor_b32 {vr(V_RW)}, {vr(V_RW)}, {vr(V_RWT)}")
-    a.label(l_par)
-    a(f"s_add_u32 {sr(S_ITER)}, {sr(S_ITER)}, {sr(S_GRID)}")
-    a(f"s_mul_i32 {sr(S_T0)}, {sr(S_TM_N)}, {sr(S_TN_N)}")
-    a(f"s_cmp_ge_u32 {sr(S_ITER)}, {sr(S_T0)}")
-    a(f"s_cbranch_scc1 {l_last}")
-    a("s_barrier")                                   # every wave done reading this tile's LDS
-    tile_setup(a, "plain", sr(S_ITER))
-    prologue_dma(a)                                  # the next tile's k-tiles 0 and 1, in flight under the pack
-    deferred_pack(a)
-    for r in range(4):
-        a(f"s_mov_b32 {sr(SRD_D + r)}, {sr(SRD_C + r)}")
-    tile_c(a, "plain")
-    a("s_waitcnt vmcnt(16)")                         # the next tile's k-tile 0 (k-tile 1's 16 pieces are younger)
-    a("s_barrier")
-    a(f"s_branch {l_tile}")
-    a.label(l_last)
-    epilogue_plain(a)                                # the last tile: stored at once
-    a.label(a.abort)
-    a("s_endpgm")
-    a.raw(f".size {name}, .-{name}")
-    body = "\n".join(a.out)
-    desc, meta = _descriptor(name)
-    return body + "\n" + desc, meta
 
 
 # ---------------------------------------------------------------- epilogues
@@ -951,7 +680,7 @@ def epilogue_rope(a: Asm):
     rounded GEMM output).  Kernarg S: cos | sin [2][S][64] fp32; fw = S (a
     multiple of 256, so a tile's 256 tokens are one sequence's), fc = Hq |
     Hkv << 16.  cos / sin rows for row block j + ROPE_DEPTH load while j is
-    rotated (counted vmcnt, as epilogue_swiglu_bwd_pipe)."""
+    rotated (counted vmcnt, as epilogue_swiglu_bwd)."""
     v = V_T
     # ---- wave-uniform: w, wm, wn, head, batch, s0 (SGPRs S_E0.. / S_T*)
     a(f"v_lshrrev_b32 {vr(v)}, 6, {vr(V_TID)}")
@@ -1310,8 +1039,7 @@ def unpack8(a: Asm, dst: int, src: int):
 
 
 def store16(a: Asm, data: int, voff: int, srd_: int, soff: int, p: int):
-    nt = " nt" if SCHED["store_nt"] else ""
-    a(f"buffer_store_dwordx4 {vr(data, 4)}, {vr(voff)}, {sr(srd_, 4)}, {sr(soff)} offen offset:{64 * p}{nt}")
+    a(f"buffer_store_dwordx4 {vr(data, 4)}, {vr(voff)}, {sr(srd_, 4)}, {sr(soff)} offen offset:{64 * p} nt")
 
 
 def epilogue_plain(a: Asm):
@@ -1324,43 +1052,28 @@ def epilogue_plain(a: Asm):
         for p in range(4):
             cvt_pack8(a, pk + 4 * p, f + 8 * p)
         for p in range(4):
-            if not SCHED["nostore"]:
-                store16(a, pk + 4 * p, V_E, SRD_C, S_E0, p)
+            store16(a, pk + 4 * p, V_E, SRD_C, S_E0, p)
         a(f"s_add_u32 {sr(S_E0)}, {sr(S_E0)}, {sr(S_E1)}")
 
 
 def silu_times(a: Asm, out: int, g: int, u: int, t: int, n: int):
     """out[e] = silu(g[e]) * u[e] = g / (1 + 2^(-g log2 e)) * u, e < n
     (batched per op: a transcendental's result is consumed n instructions
-    later, past the forwarding hazard).  epi_pk: the non-transcendental ops
-    on register pairs (v_pk_*_f32; constants -log2 e and 1.0 as pairs at
+    later, past the forwarding hazard).  The non-transcendental ops work on
+    register pairs (v_pk_*_f32; constants -log2 e and 1.0 as pairs at
     V_E + 4 / V_E + 6)."""
-    if SCHED["epi_pk"]:
-        for e in range(0, n, 2):
-            a(f"v_pk_mul_f32 {vr(t + e, 2)}, {vr(V_E + 4, 2)}, {vr(g + e, 2)}")
-        for e in range(n):
-            a(f"v_exp_f32 {vr(t + e)}, {vr(t + e)}")
-        for e in range(0, n, 2):
-            a(f"v_pk_add_f32 {vr(t + e, 2)}, {vr(V_E + 6, 2)}, {vr(t + e, 2)}")
-        for e in range(n):
-            a(f"v_rcp_f32 {vr(t + e)}, {vr(t + e)}")
-        for e in range(0, n, 2):
-            a(f"v_pk_mul_f32 {vr(t + e, 2)}, {vr(g + e, 2)}, {vr(t + e, 2)}")
-        for e in range(0, n, 2):
-            a(f"v_pk_mul_f32 {vr(out + e, 2)}, {vr(t + e, 2)}, {vr(u + e, 2)}")
-        return
-    for e in range(n):
-        a(f"v_mul_f32 {vr(t + e)}, {vr(V_E + 3)}, {vr(g + e)}")
+    for e in range(0, n, 2):
+        a(f"v_pk_mul_f32 {vr(t + e, 2)}, {vr(V_E + 4, 2)}, {vr(g + e, 2)}")
     for e in range(n):
         a(f"v_exp_f32 {vr(t + e)}, {vr(t + e)}")
-    for e in range(n):
-        a(f"v_add_f32 {vr(t + e)}, 1.0, {vr(t + e)}")
+    for e in range(0, n, 2):
+        a(f"v_pk_add_f32 {vr(t + e, 2)}, {vr(V_E + 6, 2)}, {vr(t + e, 2)}")
     for e in range(n):
         a(f"v_rcp_f32 {vr(t + e)}, {vr(t + e)}")
-    for e in range(n):
-        a(f"v_mul_f32 {vr(t + e)}, {vr(g + e)}, {vr(t + e)}")
-    for e in range(n):
-        a(f"v_mul_f32 {vr(out + e)}, {vr(t + e)}, {vr(u + e)}")
+    for e in range(0, n, 2):
+        a(f"v_pk_mul_f32 {vr(t + e, 2)}, {vr(g + e, 2)}, {vr(t + e, 2)}")
+    for e in range(0, n, 2):
+        a(f"v_pk_mul_f32 {vr(out + e, 2)}, {vr(t + e, 2)}, {vr(u + e, 2)}")
 
 
 def epilogue_swiglu_fwd(a: Asm):
@@ -1370,6 +1083,8 @@ def epilogue_swiglu_fwd(a: Asm):
     a(f"s_lshl_b32 {sr(S_E1)}, {sr(S_LDC)}, 4")
     a(f"s_mov_b32 {sr(S_T0)}, 0")
     a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDS)}, 4")
+    # (V_E + 3: the scalar form's -log2 e, read by nothing since silu_times
+    # works on pairs; the instruction stays, the kernel's bytes are pinned)
     a(f"v_mov_b32 {vr(V_E + 3)}, {-LOG2E!r}")
     for x in (4, 5):
         a(f"v_mov_b32 {vr(V_E + x)}, {-LOG2E!r}")
@@ -1388,61 +1103,46 @@ def epilogue_swiglu_fwd(a: Asm):
             store16(a, pg + 4 * p, V_E, SRD_C, S_E0, p)
             store16(a, pu + 4 * p, V_E + 2, SRD_C, S_E0, p)
         sv, ps = V_E + 88, V_E + 104
-        if SCHED["epi_f32s"]:
-            # s = silu(g) * u straight from the fp32 accumulators (no bf16 round
-            # trip: 32 VALU per row block fewer; the unfused path and round 4
-            # used the stored bf16 values, a difference below bf16 rounding)
-            for h in range(2):              # scratch: the free V_E + 56 .. 63
-                silu_times(a, sv + 8 * h, g + 8 * h, u + 8 * h, V_E + 56, 8)
-        else:
-            # s = silu(g) * u on the bf16-rounded values (what backward re-reads)
-            gf, uf, t = V_E + 56, V_E + 72, V_E + 8   # t: g/u regs, consumed
-            for p in range(2):
-                unpack8(a, gf + 8 * p, pg + 4 * p)
-                unpack8(a, uf + 8 * p, pu + 4 * p)
-            for h in range(2):              # 8 elements at a time (scratch t: 8 regs)
-                silu_times(a, sv + 8 * h, gf + 8 * h, uf + 8 * h, t, 8)
+        # s = silu(g) * u straight from the fp32 accumulators (no bf16 round
+        # trip: 32 VALU per row block fewer; the unfused path and round 4
+        # used the stored bf16 values, a difference below bf16 rounding)
+        for h in range(2):                  # scratch: the free V_E + 56 .. 63
+            silu_times(a, sv + 8 * h, g + 8 * h, u + 8 * h, V_E + 56, 8)
         for p in range(2):
             cvt_pack8(a, ps + 4 * p, sv + 8 * p)
         for p in range(2):
             store16(a, ps + 4 * p, V_E + 1, SRD_S, S_T0, p)
         a(f"s_add_u32 {sr(S_E0)}, {sr(S_E0)}, {sr(S_E1)}")
         a(f"s_add_u32 {sr(S_T0)}, {sr(S_T0)}, {sr(S_T1)}")
-        if not SCHED["epi_pipe"]:
-            a("s_waitcnt vmcnt(0)")         # (round 4) scratch reused by the next row block
-        # epi_pipe: no drain -- a store reads its data registers within two
-        # wait states of issue (cdna_hip_programming.md, asm stores), and the
-        # next row block rewrites them dozens of instructions later
+        # no drain -- a store reads its data registers within two wait states
+        # of issue (cdna_hip_programming.md, asm stores), and the next row
+        # block rewrites them dozens of instructions later
 
 
 EPI_DEPTH = 6    # SwiGLU backward: gu row blocks loaded this many rounds ahead (staging in the free fragment VGPRs)
 
 
+
 def epilogue_swiglu_bwd(a: Asm):
-    if SCHED["epi_pipe"]:
-        return epilogue_swiglu_bwd_pipe(a)
-    return epilogue_swiglu_bwd_r4(a)
-
-
-def epilogue_swiglu_bwd_pipe(a: Asm):
-    """The SwiGLU backward epilogue with its gu loads software-pipelined:
-    16 rounds (8 row blocks x 2 column halves), round r's 4 loads issued
-    EPI_DEPTH rounds ahead into staging slots in the main loop's fragment
-    VGPRs (free here), each round waiting only for its own loads (counted
-    vmcnt: VMEM completes in issue order) instead of draining every load
-    and store per round -- the round-4 form exposed a full memory latency 32
-    times per tile (59 % MFMA busy in the model, profiles/r5_pmc)."""
+    """The SwiGLU backward epilogue (acc = ds, never stored; gu rows: gate at
+    n, up at F + n) with its gu loads software-pipelined: 16 rounds (8 row
+    blocks x 2 column halves), round r's 4 loads issued EPI_DEPTH rounds
+    ahead into staging slots in the main loop's fragment VGPRs (free here),
+    each round waiting only for its own loads (counted vmcnt: VMEM completes
+    in issue order) instead of draining every load and store per round -- the
+    round-4 form exposed a full memory latency 32 times per tile (59 % MFMA
+    busy in the model, profiles/r5_pmc)."""
     a(f"s_mov_b32 {sr(S_E0)}, 0")                             # dgu row block
     a(f"s_lshl_b32 {sr(S_E1)}, {sr(S_LDC)}, 4")
     a(f"s_mov_b32 {sr(S_T2)}, 0")                             # gu row block of the next prefetch
     a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDS)}, 4")
-    a(f"v_mov_b32 {vr(V_E + 4)}, {-LOG2E!r}")
-    if SCHED["epi_pk"]:   # pairs: -log2 e (V_E + 4), 1.0 (V_E + 6), -1.0 (V_E + 10)
-        a(f"v_mov_b32 {vr(V_E + 5)}, {-LOG2E!r}")
-        for x in (6, 7):
-            a(f"v_mov_b32 {vr(V_E + x)}, 1.0")
-        for x in (10, 11):
-            a(f"v_mov_b32 {vr(V_E + x)}, -1.0")
+    # pairs (the math runs on v_pk_*_f32): -log2 e (V_E + 4), 1.0 (V_E + 6), -1.0 (V_E + 10)
+    for x in (4, 5):
+        a(f"v_mov_b32 {vr(V_E + x)}, {-LOG2E!r}")
+    for x in (6, 7):
+        a(f"v_mov_b32 {vr(V_E + x)}, 1.0")
+    for x in (10, 11):
+        a(f"v_mov_b32 {vr(V_E + x)}, -1.0")
     rounds = [(j, half) for j in range(8) for half in range(2)]
     D = EPI_DEPTH
     seq: list = []     # VMEM ops in issue order: ("L" | "S", round)
@@ -1450,12 +1150,8 @@ def epilogue_swiglu_bwd_pipe(a: Asm):
     def slot(r):
         return V_FX0 + 16 * (r % D)                           # lg = slot, lu = slot + 8
 
-    noload, novalu, nostore = SCHED["epi_noload"], SCHED["epi_novalu"], SCHED["epi_nostore"]
-
     def issue_loads(r):
         j, half = rounds[r]
-        if noload:
-            return
         lg, lu = slot(r), slot(r) + 8
         for q, p in enumerate((2 * half, 2 * half + 1)):
             a(f"buffer_load_dwordx4 {vr(lg + 4 * q, 4)}, {vr(V_E + 1)}, {sr(SRD_S, 4)}, {sr(S_T2)} offen offset:{64 * p}")
@@ -1468,21 +1164,6 @@ def epilogue_swiglu_bwd_pipe(a: Asm):
         issue_loads(r)
     for r, (j, half) in enumerate(rounds):
         ps_ = (2 * half, 2 * half + 1)
-        if novalu:   # DIAGNOSTIC: the loaded gu goes straight back out as dgu
-            last = max(i for i, x in enumerate(seq) if x == ("L", r))
-            a(f"s_waitcnt vmcnt({min(63, len(seq) - last - 1)})")
-            lg, lu = slot(r), slot(r) + 8
-            if not nostore:
-                for q, p in enumerate(ps_):
-                    store16(a, lg + 4 * q, V_E, SRD_C, S_E0, p)
-                    store16(a, lu + 4 * q, V_E + 2, SRD_C, S_E0, p)
-                seq.extend([("S", r)] * 4)
-            a("s_nop 1")
-            if r + D < len(rounds):
-                issue_loads(r + D)
-            if half == 1:
-                a(f"s_add_u32 {sr(S_E0)}, {sr(S_E0)}, {sr(S_E1)}")
-            continue
         d = V_E + 24                        # 16 f32: ds (no memory dependency: first)
         for q, p in enumerate(ps_):
             read_pair(a, d + 8 * q, p, j)
@@ -1491,12 +1172,9 @@ def epilogue_swiglu_bwd_pipe(a: Asm):
             cvt_pack8(a, pd + 4 * q, d + 8 * q)
         for q in range(2):
             unpack8(a, d + 8 * q, pd + 4 * q)
-        if noload:   # DIAGNOSTIC: ds stands in for both gate and up
-            lg = lu = pd
-        else:
-            last = max(i for i, x in enumerate(seq) if x == ("L", r))
-            a(f"s_waitcnt vmcnt({min(63, len(seq) - last - 1)})")   # this round's loads only
-            lg, lu = slot(r), slot(r) + 8
+        last = max(i for i, x in enumerate(seq) if x == ("L", r))
+        a(f"s_waitcnt vmcnt({min(63, len(seq) - last - 1)})")   # this round's loads only
+        lg, lu = slot(r), slot(r) + 8
         gf, uf = V_E + 48, V_E + 64
         for q in range(2):
             unpack8(a, gf + 8 * q, lg + 4 * q)
@@ -1504,131 +1182,49 @@ def epilogue_swiglu_bwd_pipe(a: Asm):
         if r + D < len(rounds):
             issue_loads(r + D)              # into the slot just unpacked
         sg, tmp, tt = V_E + 80, V_E + 96, V_E + 8
-        if SCHED["epi_pk"]:                 # the same math on register pairs
-            for e in range(0, 16, 2):       # sg = 1 / (1 + exp(-g))
-                a(f"v_pk_mul_f32 {vr(sg + e, 2)}, {vr(V_E + 4, 2)}, {vr(gf + e, 2)}")
-            for e in range(16):
-                a(f"v_exp_f32 {vr(sg + e)}, {vr(sg + e)}")
-            for e in range(0, 16, 2):
-                a(f"v_pk_add_f32 {vr(sg + e, 2)}, {vr(V_E + 6, 2)}, {vr(sg + e, 2)}")
-            for e in range(16):
-                a(f"v_rcp_f32 {vr(sg + e)}, {vr(sg + e)}")
-            for e in range(0, 16, 2):       # du = d * g * sg  -> tmp
-                a(f"v_pk_mul_f32 {vr(tmp + e, 2)}, {vr(d + e, 2)}, {vr(gf + e, 2)}")
-                a(f"v_pk_mul_f32 {vr(tmp + e, 2)}, {vr(tmp + e, 2)}, {vr(sg + e, 2)}")
-            for e in range(0, 16, 2):       # dg = d * u * sg * (1 + g (1 - sg)) -> uf
-                a(f"v_pk_fma_f32 {vr(tt, 2)}, {vr(sg + e, 2)}, {vr(V_E + 10, 2)}, {vr(V_E + 6, 2)}")
-                a(f"v_pk_fma_f32 {vr(tt, 2)}, {vr(gf + e, 2)}, {vr(tt, 2)}, {vr(V_E + 6, 2)}")
-                a(f"v_pk_mul_f32 {vr(uf + e, 2)}, {vr(d + e, 2)}, {vr(uf + e, 2)}")
-                a(f"v_pk_mul_f32 {vr(uf + e, 2)}, {vr(uf + e, 2)}, {vr(sg + e, 2)}")
-                a(f"v_pk_mul_f32 {vr(uf + e, 2)}, {vr(uf + e, 2)}, {vr(tt, 2)}")
-        else:
-            for e in range(16):             # sg = 1 / (1 + exp(-g))
-                a(f"v_mul_f32 {vr(sg + e)}, {vr(V_E + 4)}, {vr(gf + e)}")
-            for e in range(16):
-                a(f"v_exp_f32 {vr(sg + e)}, {vr(sg + e)}")
-            for e in range(16):
-                a(f"v_add_f32 {vr(sg + e)}, 1.0, {vr(sg + e)}")
-            for e in range(16):
-                a(f"v_rcp_f32 {vr(sg + e)}, {vr(sg + e)}")
-            for e in range(16):             # du = d * g * sg  -> tmp
-                a(f"v_mul_f32 {vr(tmp + e)}, {vr(d + e)}, {vr(gf + e)}")
-                a(f"v_mul_f32 {vr(tmp + e)}, {vr(tmp + e)}, {vr(sg + e)}")
-            for e in range(16):             # dg = d * u * sg * (1 + g (1 - sg)) -> uf
-                a(f"v_sub_f32 {vr(tt)}, 1.0, {vr(sg + e)}")
-                a(f"v_fma_f32 {vr(tt)}, {vr(gf + e)}, {vr(tt)}, 1.0")
-                a(f"v_mul_f32 {vr(uf + e)}, {vr(d + e)}, {vr(uf + e)}")
-                a(f"v_mul_f32 {vr(uf + e)}, {vr(uf + e)}, {vr(sg + e)}")
-                a(f"v_mul_f32 {vr(uf + e)}, {vr(uf + e)}, {vr(tt)}")
+        for e in range(0, 16, 2):           # sg = 1 / (1 + exp(-g))
+            a(f"v_pk_mul_f32 {vr(sg + e, 2)}, {vr(V_E + 4, 2)}, {vr(gf + e, 2)}")
+        for e in range(16):
+            a(f"v_exp_f32 {vr(sg + e)}, {vr(sg + e)}")
+        for e in range(0, 16, 2):
+            a(f"v_pk_add_f32 {vr(sg + e, 2)}, {vr(V_E + 6, 2)}, {vr(sg + e, 2)}")
+        for e in range(16):
+            a(f"v_rcp_f32 {vr(sg + e)}, {vr(sg + e)}")
+        for e in range(0, 16, 2):           # du = d * g * sg  -> tmp
+            a(f"v_pk_mul_f32 {vr(tmp + e, 2)}, {vr(d + e, 2)}, {vr(gf + e, 2)}")
+            a(f"v_pk_mul_f32 {vr(tmp + e, 2)}, {vr(tmp + e, 2)}, {vr(sg + e, 2)}")
+        for e in range(0, 16, 2):           # dg = d * u * sg * (1 + g (1 - sg)) -> uf
+            a(f"v_pk_fma_f32 {vr(tt, 2)}, {vr(sg + e, 2)}, {vr(V_E + 10, 2)}, {vr(V_E + 6, 2)}")
+            a(f"v_pk_fma_f32 {vr(tt, 2)}, {vr(gf + e, 2)}, {vr(tt, 2)}, {vr(V_E + 6, 2)}")
+            a(f"v_pk_mul_f32 {vr(uf + e, 2)}, {vr(d + e, 2)}, {vr(uf + e, 2)}")
+            a(f"v_pk_mul_f32 {vr(uf + e, 2)}, {vr(uf + e, 2)}, {vr(sg + e, 2)}")
+            a(f"v_pk_mul_f32 {vr(uf + e, 2)}, {vr(uf + e, 2)}, {vr(tt, 2)}")
         pdg, pdu = V_E + 40, V_E + 112      # 8 + 4 regs: reuse gf for the last du pair
         for q in range(2):
             cvt_pack8(a, pdg + 4 * q, uf + 8 * q)
         cvt_pack8(a, pdu, tmp)
         cvt_pack8(a, gf, tmp + 8)
-        if not nostore:
-            for q, p in enumerate(ps_):
-                store16(a, pdg + 4 * q, V_E, SRD_C, S_E0, p)
-            store16(a, pdu, V_E + 2, SRD_C, S_E0, ps_[0])
-            store16(a, gf, V_E + 2, SRD_C, S_E0, ps_[1])
-            seq.extend([("S", r)] * 4)
+        for q, p in enumerate(ps_):
+            store16(a, pdg + 4 * q, V_E, SRD_C, S_E0, p)
+        store16(a, pdu, V_E + 2, SRD_C, S_E0, ps_[0])
+        store16(a, gf, V_E + 2, SRD_C, S_E0, ps_[1])
+        seq.extend([("S", r)] * 4)
         a("s_nop 1")                        # store data read before the next round rewrites it
         if half == 1:
             a(f"s_add_u32 {sr(S_E0)}, {sr(S_E0)}, {sr(S_E1)}")
 
-
-def epilogue_swiglu_bwd_r4(a: Asm):
-    """acc = ds (never stored).  gu rows: gate at n, up at F + n; pairs p of
-    fragments give 8 consecutive n per lane: 16-byte loads and stores."""
-    a(f"s_mov_b32 {sr(S_E0)}, 0")                             # dgu row block
-    a(f"s_lshl_b32 {sr(S_E1)}, {sr(S_LDC)}, 4")
-    a(f"s_mov_b32 {sr(S_T0)}, 0")                             # gu row block
-    a(f"s_lshl_b32 {sr(S_T1)}, {sr(S_LDS)}, 4")
-    a(f"v_mov_b32 {vr(V_E + 4)}, {-LOG2E!r}")
-    for j in range(8):
-        for half in range(2):               # pairs p = 2 half, 2 half + 1
-            ps_ = (2 * half, 2 * half + 1)
-            lg, lu = V_E + 8, V_E + 16      # loaded packed gate / up (4 regs per pair)
-            for q, p in enumerate(ps_):
-                a(f"buffer_load_dwordx4 {vr(lg + 4 * q, 4)}, {vr(V_E + 1)}, {sr(SRD_S, 4)}, {sr(S_T0)} offen offset:{64 * p}")
-                a(f"buffer_load_dwordx4 {vr(lu + 4 * q, 4)}, {vr(V_E + 3)}, {sr(SRD_S, 4)}, {sr(S_T0)} offen offset:{64 * p}")
-            d = V_E + 24                    # 16 f32: ds
-            for q, p in enumerate(ps_):
-                read_pair(a, d + 8 * q, p, j)
-            pd = V_E + 40                   # bf16-rounded ds, then unpacked
-            for q in range(2):
-                cvt_pack8(a, pd + 4 * q, d + 8 * q)
-            for q in range(2):
-                unpack8(a, d + 8 * q, pd + 4 * q)
-            a("s_waitcnt vmcnt(0)")
-            gf, uf = V_E + 48, V_E + 64
-            for q in range(2):
-                unpack8(a, gf + 8 * q, lg + 4 * q)
-                unpack8(a, uf + 8 * q, lu + 4 * q)
-            sg, tmp = V_E + 80, V_E + 96
-            for e in range(16):             # sg = 1 / (1 + exp(-g))
-                a(f"v_mul_f32 {vr(sg + e)}, {vr(V_E + 4)}, {vr(gf + e)}")
-            for e in range(16):
-                a(f"v_exp_f32 {vr(sg + e)}, {vr(sg + e)}")
-            for e in range(16):
-                a(f"v_add_f32 {vr(sg + e)}, 1.0, {vr(sg + e)}")
-            for e in range(16):
-                a(f"v_rcp_f32 {vr(sg + e)}, {vr(sg + e)}")
-            for e in range(16):             # du = d * g * sg  -> tmp
-                a(f"v_mul_f32 {vr(tmp + e)}, {vr(d + e)}, {vr(gf + e)}")
-                a(f"v_mul_f32 {vr(tmp + e)}, {vr(tmp + e)}, {vr(sg + e)}")
-            for e in range(16):             # dg = d * u * sg * (1 + g (1 - sg)) -> uf
-                a(f"v_sub_f32 {vr(lg)}, 1.0, {vr(sg + e)}")
-                a(f"v_fma_f32 {vr(lg)}, {vr(gf + e)}, {vr(lg)}, 1.0")
-                a(f"v_mul_f32 {vr(uf + e)}, {vr(d + e)}, {vr(uf + e)}")
-                a(f"v_mul_f32 {vr(uf + e)}, {vr(uf + e)}, {vr(sg + e)}")
-                a(f"v_mul_f32 {vr(uf + e)}, {vr(uf + e)}, {vr(lg)}")
-            pdg, pdu = V_E + 40, V_E + 112  # 8 + 4 regs: reuse gf for the last du pair
-            for q in range(2):
-                cvt_pack8(a, pdg + 4 * q, uf + 8 * q)
-            cvt_pack8(a, pdu, tmp)
-            cvt_pack8(a, gf, tmp + 8)
-            for q, p in enumerate(ps_):
-                store16(a, pdg + 4 * q, V_E, SRD_C, S_E0, p)
-            store16(a, pdu, V_E + 2, SRD_C, S_E0, ps_[0])
-            store16(a, gf, V_E + 2, SRD_C, S_E0, ps_[1])
-            a("s_waitcnt vmcnt(0)")         # scratch registers are reused next round
-        a(f"s_add_u32 {sr(S_E0)}, {sr(S_E0)}, {sr(S_E1)}")
-        a(f"s_add_u32 {sr(S_T0)}, {sr(S_T0)}, {sr(S_T1)}")
 
 
 # ---------------------------------------------------------------- kernel
 def kernel(epi: str, trace: bool = False, variant: str = "") -> tuple[str, str]:
     """trace=True: the diagnostic trace variant of the plain kernel (markers
     into a host-coherent buffer in the S slot; toa_gemm_tn_asm_trace).
-    variant: an A/B arm of the plain kernel (PLAIN_VARIANTS)."""
+    variant: the name suffix of a kernel generated under _with_knobs (the
+    persistent arms, the timing kernels)."""
     name = "toa_gemm_tn_asm_trace" if trace else f"toa_gemm_tn_asm_{epi}" + (f"_{variant}" if variant else "")
-    if SCHED["defer"]:
-        assert epi == "plain" and not trace and not SCHED["timing"] and SCHED["persist"] and SCHED["map"]
-        return kernel_defer(name)
     if SCHED["timing"]:
         name = "toa_gemm_tn_asm_timing" + ("" if SCHED["timing"] == 1 else str(SCHED["timing"]))
     a = Asm(prefix=("trace_" if trace else epi + "_" + (variant + "_" if variant else "")))
-    tb = (lambda base: base) if trace else (lambda base: 0)
     a.raw(f".globl {name}")
     a.raw(".p2align 8")
     a.raw(f".type {name},@function")
@@ -1644,10 +1240,9 @@ def kernel(epi: str, trace: bool = False, variant: str = "") -> tuple[str, str]:
             a(ins)
     # --- prologue DMA: tile 0 -> stage 0, tile 1 -> stage 1
     prologue_dma(a)
-    if SCHED["zero_late"]:
-        # 256 accumulator writes while the first tiles are in flight, not
-        # ahead of their DMA (~1k issue cycles per tile off the critical path)
-        zero_acc(a)
+    # 256 accumulator writes while the first tiles are in flight, not ahead
+    # of their DMA (~1k issue cycles per tile off the critical path)
+    zero_acc(a)
     # both stages toggled twice: M0 bases are back at stage 0 for tile 2
     a("s_waitcnt vmcnt(16)")                       # own tile-0 pieces
     a("s_barrier")                                 # everyone's
@@ -1670,37 +1265,15 @@ def kernel(epi: str, trace: bool = False, variant: str = "") -> tuple[str, str]:
     l_loop, l_tail = a.fresh("loop"), a.fresh("tail")
     a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
     a(f"s_cbranch_scc1 {l_tail}")
-    dual = SCHED["dual"]
-    if dual:
-        # two loop bodies, picked by the SIMD id's low bit (HW_ID[4]): the
-        # waves of SIMDs 1 and 3 run the `dual` map, whose DMA pieces and
-        # reads sit one MFMA away from the others'.  Both bodies have the
-        # same barriers, so the workgroup stays in step.
-        assert SCHED["map"] and not SCHED["timing"]
-        l_loop1 = a.fresh("loop1")
-        a(f"s_getreg_b32 {sr(S_T0)}, hwreg(HW_REG_HW_ID, 4, 1)")
-        a(f"s_cmp_eq_u32 {sr(S_T0)}, 0")
-        a(f"s_cbranch_scc0 {l_loop1}")
-    if SCHED["align"]:
-        a(".p2alignl 6, 0xbf800000")   # loop head on a 64-byte boundary (s_nop padding)
+    a(".p2alignl 6, 0xbf800000")   # loop head on a 64-byte boundary (s_nop padding)
     a.label(l_loop)
-    it = iteration_map if SCHED["map"] else iteration
-    it(a, with_dma=True, next_reads=True, vm_after_dma=16, trace_base=tb(100))
+    iteration_map(a, with_dma=True, next_reads=True)
     a(f"s_sub_u32 {sr(S_LOOP)}, {sr(S_LOOP)}, 1")
     a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
     a(f"s_cbranch_scc0 {l_loop}")
-    if dual:
-        a(f"s_branch {l_tail}")
-        if SCHED["align"]:
-            a(".p2alignl 6, 0xbf800000")
-        a.label(l_loop1)
-        iteration_map(a, with_dma=True, next_reads=True, vm_after_dma=16, mapname=dual)
-        a(f"s_sub_u32 {sr(S_LOOP)}, {sr(S_LOOP)}, 1")
-        a(f"s_cmp_eq_u32 {sr(S_LOOP)}, 0")
-        a(f"s_cbranch_scc0 {l_loop1}")
     a.label(l_tail)
-    it(a, with_dma=False, next_reads=True, vm_after_dma=0, trace_base=tb(200))
-    it(a, with_dma=False, next_reads=False, vm_after_dma=0, trace_base=tb(300))
+    iteration_map(a, with_dma=False, next_reads=True)
+    iteration_map(a, with_dma=False, next_reads=False)
     if epi == "plain" and not trace and not variant:
         stage_exit(a, 2)
     if timing:
@@ -1713,12 +1286,11 @@ def kernel(epi: str, trace: bool = False, variant: str = "") -> tuple[str, str]:
             a(ins)
     if persist:
         persistent_next(a, epi, l_tile)
-    if not SCHED["epi_none"]:   # (the "none" arm: DIAGNOSTIC, the main loop alone)
-        if epi != "rope":
-            epi_offsets(a, epi)
-        {"plain": epilogue_plain, "swiglu_fwd": epilogue_swiglu_fwd, "swiglu_bwd": epilogue_swiglu_bwd,
-         "rope": epilogue_rope, "delta": epilogue_delta, "resadd": epilogue_resadd}[epi](a)
-    if trace or timing or SCHED["drain_end"]:
+    if epi != "rope":
+        epi_offsets(a, epi)
+    {"plain": epilogue_plain, "swiglu_fwd": epilogue_swiglu_fwd, "swiglu_bwd": epilogue_swiglu_bwd,
+     "rope": epilogue_rope, "delta": epilogue_delta, "resadd": epilogue_resadd}[epi](a)
+    if trace or timing:
         a("s_waitcnt vmcnt(0)")
     # else: end with the epilogue's stores still in flight -- the wave's end
     # does not wait for them, so the next workgroup on this CU starts its
@@ -1835,7 +1407,6 @@ def persistent_next(a: Asm, epi: str, l_tile: str):
 # LDS per stage: X half (HALF) + W image (wgrad_gen.OPER) = 72640 B, two
 # stages 145280 B, the delta epilogue's 1 KiB behind them.
 NN_EPIS = ("plain", "swiglu_bwd", "delta")
-NN_MAP = "lib0"
 # W read bases and stage toggles beside V_RW / V_RWT (even fragments, rows +0): rows +4, and both for the odd
 # fragments (main loop only: epilogue scratch)
 V_RWH, V_RWHT, V_RWO, V_RWOT, V_RWHO, V_RWHOT = (V_E + k for k in range(4, 10))
@@ -1949,12 +1520,11 @@ def nn_prologue_dma(a: Asm):
 
 
 def iteration_nn(a: Asm, with_dma: bool, next_reads: bool):
-    """One 64-k tile of the NN loop on slot map NN_MAP (the keys of
-    iteration_map): a W slot carries the fragment's two transposed reads, so
+    """One 64-k tile of the NN loop on SLOT_MAP: a W slot carries the fragment's two transposed reads, so
     a sub-step issues 8 + 16 reads; the 16 DMA pieces, both barriers and the
     counted next-tile wait sit where the TN loop has them."""
-    m = SLOT_MAPS[NN_MAP]
-    split, lag = m.get("split", 0), m.get("m0_lag", 0)
+    m = SLOT_MAP
+    split, lag = m["split"], m["m0_lag"]
     slots: dict[int, list[str]] = {n: [] for n in range(128)}
     for j, n in enumerate(m["x1"]):
         slots[n].append(frag_read("x", j, 1))
@@ -1977,7 +1547,7 @@ def iteration_nn(a: Asm, with_dma: bool, next_reads: bool):
                 if j < 7:
                     assert lag >= 1 and pos[j + 1] > n + lag      # an MFMA between an M0 write and the next piece
                     slots[n + lag].append(f"s_add_u32 m0, m0, {nn_m0_step(half, j)}")
-            adv = m.get("adv", {}).get(half, pos[-1])
+            adv = m["adv"][half]
             assert pos[-1] <= adv < 128
             slots[adv] += nn_advance(half) + [f"s_xor_b32 {sr(m0)}, {sr(m0)}, {sr(m0 + 1)}"]
         assert max(m["xdma"]) + lag < min(m["wdma"]) - 1          # one running M0
@@ -2206,20 +1776,10 @@ PROBE_VBASE = 128
 PROBE_WORDS = PROBE_VBASE + 8 * 256
 
 
-# A/B arms of the plain kernel, launched by index through toa_gemm_asm_variant
-# (scripts/asm_gemm_bench.py --variants): layout / schedule knobs against the
-# product kernel, measured in one process.  Index 0 is the product kernel.
-PLAIN_VARIANTS = (
-    ("v1", {"map": "spread", "zero_late": False}),   # the round-4 product kernel
-    ("v2", {"zero_late": False}),           # accumulators zeroed ahead of the prologue DMA (round 4)
-    ("v3", {"persist": True}),              # persistent: a workgroup per CU walks its tiles, next tile staged under the epilogue
-    ("v4", {"nostore": True, "diag": True}),  # DIAGNOSTIC: no C stores (what the epilogue's stores cost); C is not written
-    ("v5", {"dual": "lib1"}),               # the library's second loop body on odd SIMDs
-    ("v6", {"store_same": True, "diag": True}),  # DIAGNOSTIC: every workgroup stores tile (0, 0) (L2-hot writes)
-    ("v7", {"store_nt": False}),            # C stores without the non-temporal hint
-    ("v8", {"persist": True, "store_nt": False}),
-    ("v9", {"persist": True, "defer": True}),   # persistent, C stores deferred into the next tile's first k-tile
-)
+# The persistent plain kernel (a workgroup per CU walks its tiles, the next
+# tile staged under the epilogue), launched by toa_gemm_asm_set_persist /
+# TOA_ASM_PERSIST.
+PLAIN_VARIANTS = (("v3", {"persist": True}),)
 # measured (profiles/r4_asm_gemm/ab1..diag2): MFMAs on 8-byte boundaries, ending
 # with the epilogue's stores in flight, two barriers per tile and the wait 16
 # MFMAs earlier all within noise (+-1.5 %); LDS lines of 1040 B (same speed
@@ -2229,15 +1789,13 @@ PLAIN_VARIANTS = (
 # read taken into the product kernel (+1..+4 %); an L2 prefetch of the tile two
 # beyond the DMA (one 4-B load per line, its own bounded resources) -16..-24 %
 # (profiles/r4_asm_gemm/ab3): the extra loads share the counted vmcnt waits.
-# Round 5 (profiles/r5_lib/forms.log): the "lib0" placement (barriers one MFMA
+# Round 5 (profiles/r5_asm_gemm/): the SLOT_MAP placement (barriers one MFMA
 # after their waits, M0 / resource advances one MFMA after the pieces) +0.5..2 %
-# over "spread" at every form, taken into the product kernel; the library's
-# second loop body for odd SIMDs (with and without MFMA alignment) -1..-3 %.
+# over the same slots without the lags at every form, taken into the product
+# kernel; the library's second loop body for odd SIMDs (with and without MFMA
+# alignment) -1..-3 %.  The arms themselves are pruned (docs/kernels.md).
 
 
-# DIAGNOSTIC arms of the fused SwiGLU backward (wrong outputs by design),
-# launched by index through toa_gemm_asm_swiglu_bwd_variant: where the fused
-# epilogue's time goes (scripts/asm_gemm_bench.py --swiglu-variants).
 # Persistent fused SwiGLU GEMMs (one workgroup per CU walks its tiles; the
 # next tile's first two k-tiles are staged before the current tile's
 # epilogue, so its gu loads / dgu stores overlap that DMA instead of a fresh
@@ -2245,84 +1803,40 @@ PLAIN_VARIANTS = (
 # toa_gemm_asm_set_swiglu_persist.
 SWIGLU_PERSIST_VARIANTS = (("swiglu_fwd", "p1", {"persist": True}), ("swiglu_bwd", "p1", {"persist": True}))
 
-SWIGLU_BWD_VARIANTS = (
-    ("b1", {"epi_none": True}),          # the main loop alone
-    ("b2", {"epi_noload": True}),        # math + stores, no gu loads
-    ("b3", {"epi_novalu": True}),        # gu loads + dgu stores, no math
-    ("b4", {"epi_nostore": True}),       # loads + math, no stores
-    ("b5", {"epi_noload": True, "epi_nostore": True}),   # math alone
-)
+# The timing diagnostics of the plain kernel (toa_gemm_asm_timing).
+TIMING_VARIANTS = (("timing", {"timing": 1}), ("timing2", {"timing": 2}))
 
 
 def _with_knobs(knobs: dict, fn):
-    """Run fn() with the layout globals / SCHED entries in `knobs` overridden."""
-    g = globals()
-    saved = {k: g[k] for k in ("LINE", "HALF", "STAGE", "LDS_BYTES")}
-    saved_sched = dict(SCHED)
+    """Run fn() with the SCHED entries in `knobs` overridden."""
+    saved = dict(SCHED)
+    assert set(knobs) <= set(SCHED)
+    SCHED.update(knobs)
     try:
-        if "LINE" in knobs:
-            g["LINE"] = knobs["LINE"]
-            g["HALF"] = 32 * g["LINE"]
-            g["STAGE"] = 2 * g["HALF"]
-            g["LDS_BYTES"] = 2 * g["STAGE"]
-        SCHED.update({k: v for k, v in knobs.items() if k in SCHED})
         return fn()
     finally:
-        g.update(saved)
-        SCHED.clear()
-        SCHED.update(saved_sched)
+        SCHED.update(saved)
 
 
 def generate() -> str:
+    import attn_bwd_gen  # the attention forward, the dK / dV backward and the weight-gradient
+    import attn_gen      # kernel share this code object (lazy: they import this module)
+    import wgrad_gen
+
+    kernels = [kernel(epi) for epi in EPIS]
+    kernels += [_with_knobs(knobs, lambda: kernel("plain", variant=vname)) for vname, knobs in PLAIN_VARIANTS]
+    kernels += [_with_knobs(knobs, lambda: kernel(epi, variant=vname)) for epi, vname, knobs in SWIGLU_PERSIST_VARIANTS]
+    kernels += [wgrad_gen.kernel(), *attn_gen.all_kernels(), probe_kernel(), kernel("plain", trace=True)]
+    kernels += [_with_knobs(knobs, lambda: kernel("plain", variant=vname)) for vname, knobs in TIMING_VARIANTS]
+    kernels += attn_bwd_gen.all_kernels()
+    kernels += [kernel_nn(epi) for epi in NN_EPIS]   # the data gradients on W as stored
     parts = ['.amdgcn_target "amdgcn-amd-amdhsa--gfx950"', ".amdhsa_code_object_version 5", ".text"]
-    metas = []
-    for epi in EPIS:
-        body, meta = kernel(epi)
-        parts.append(body)
-        metas.append(meta)
-    for epi in ("swiglu_fwd", "swiglu_bwd"):   # round-4 epilogues (per-round drains): in-model A/B arms
-        body, meta = _with_knobs({"epi_pipe": False, "epi_pk": False, "epi_f32s": False},
-                                 lambda: kernel(epi, variant="r4"))
-        parts.append(body)
-        metas.append(meta)
-    for vname, knobs in PLAIN_VARIANTS:
-        body, meta = _with_knobs(knobs, lambda: kernel("plain", variant=vname))
-        parts.append(body)
-        metas.append(meta)
-    for vname, knobs in SWIGLU_BWD_VARIANTS:
-        body, meta = _with_knobs(knobs, lambda: kernel("swiglu_bwd", variant=vname))
-        parts.append(body)
-        metas.append(meta)
-    for epi, vname, knobs in SWIGLU_PERSIST_VARIANTS:
-        body, meta = _with_knobs(knobs, lambda: kernel(epi, variant=vname))
-        parts.append(body)
-        metas.append(meta)
-    import attn_gen   # the attention forward and the weight-gradient kernel share this code object
-    import wgrad_gen  # (lazy: both import this module)
-
-    def wgrad_round4():
-        saved = dict(wgrad_gen.KNOBS)
-        wgrad_gen.KNOBS.update(map="spread", zero_late=False)
-        try:
-            return wgrad_gen.kernel("v1")
-        finally:
-            wgrad_gen.KNOBS.clear()
-            wgrad_gen.KNOBS.update(saved)
-
-    import attn_bwd_gen  # the attention dK / dV backward, same code object
-
-    for body, meta in (wgrad_gen.kernel(), wgrad_round4(), *attn_gen.all_kernels(), probe_kernel(), kernel("plain", trace=True),
-                       _with_knobs({"timing": 1}, lambda: kernel("plain", variant="timing")),
-                       _with_knobs({"timing": 2}, lambda: kernel("plain", variant="timing2")),
-                       *attn_bwd_gen.all_kernels(),
-                       *(kernel_nn(epi) for epi in NN_EPIS)):   # the data gradients on W as stored
-        parts.append(body)
-        metas.append(meta)
+    parts += [body for body, _ in kernels]
     # what hipcc emits after the last kernel: s_nop padding, so the
     # instruction prefetcher never runs off the end of the code object
     parts.append(".text\n.p2alignl 6, 3212836864\n.fill 256, 4, 3212836864")   # s_nop 0
-    parts.append(".amdgpu_metadata\n---\namdhsa.version:\n  - 1\n  - 2\namdhsa.target: amdgcn-amd-amdhsa--gfx950\namdhsa.kernels:\n" + "".join(metas)
-                 + "...\n.end_amdgpu_metadata")
+    parts.append(".amdgpu_metadata\n---\namdhsa.version:\n  - 1\n  - 2\namdhsa.target: amdgcn-amd-amdhsa--gfx950\namdhsa.kernels:\n"
+                 + "".join(meta for _, meta in kernels) + "...\n.end_amdgpu_metadata")
     return "\n".join(parts) + "\n"
 
 

@@ -120,12 +120,6 @@ V_TGALO, V_TGAHI, V_TGBLO, V_TGBHI = 140, 141, 142, 143
 V_E = 144                                        # 144..255 epilogue scratch
 V_SQ = V_E + 100                                 # 244..247: sum-of-squares accumulators (whole-K tiles)
 
-# slot map: the forward kernel's product placement (gemm_gen.SLOT_MAPS
-# "lib0": barriers one MFMA after their waits, M0 / resource advances one
-# MFMA behind the pieces); KNOBS["map"] selects another for an A/B arm
-KNOBS = {"map": "lib0", "zero_late": True}
-
-
 def prologue(a: Asm):
     a(f"s_load_dwordx16 {sr(4, 16)}, s[0:1], 0x0")
     a(f"s_load_dwordx4 {sr(20, 4)}, s[0:1], 0x40")
@@ -315,8 +309,6 @@ def prologue(a: Asm):
     for base, tg in ((V_RALO, V_TGALO), (V_RAHI, V_TGAHI), (V_RBLO, V_TGBLO), (V_RBHI, V_TGBHI)):
         a(f"v_add_u32 {vr(tg)}, {STAGE}, {vr(base)}")
         a(f"v_xor_b32 {vr(tg)}, {vr(tg)}, {vr(base)}")
-    if not KNOBS["zero_late"]:
-        zero_acc(a)
 
 
 def zero_acc(a: Asm):
@@ -411,10 +403,11 @@ def mfma(i: int, j: int, sub: int) -> str:
 
 
 def iteration(a: Asm, with_dma: bool, next_reads: bool):
-    """One 64-row (t) tile on the forward kernel's slot map (the same keys:
-    split / m0_lag / adv, gemm_gen.iteration_map)."""
-    m = G.SLOT_MAPS[KNOBS["map"]]
-    split, lag = m.get("split", 0), m.get("m0_lag", 0)
+    """One 64-row (t) tile on the forward kernel's slot map (gemm_gen.SLOT_MAP:
+    barriers one MFMA after their waits, M0 / resource advances one MFMA
+    behind the pieces)."""
+    m = G.SLOT_MAP
+    split, lag = m["split"], m["m0_lag"]
     slots: dict[int, list[str]] = {n: [] for n in range(128)}
     for j, n in enumerate(m["x1"]):
         slots[n] += frag_reads("a", j, 1)
@@ -436,7 +429,7 @@ def iteration(a: Asm, with_dma: bool, next_reads: bool):
                 if j < 7:
                     assert p[j + 1] > n + lag
                     slots[n + lag].append(f"s_add_u32 m0, m0, {blockbase(j + 1) - blockbase(j)}")
-            adv = m.get("adv", {}).get("x" if half == "a" else "w", p[-1])
+            adv = m["adv"]["x" if half == "a" else "w"]
             slots[adv] += advance(half) + [f"s_xor_b32 {sr(m0)}, {sr(m0)}, {sr(m0 + 1)}"]
         vm = sum(1 for n in m["xdma"] + m["wdma"] if n < m["wait"])
     if next_reads:
@@ -556,9 +549,9 @@ def sumsq_store(a: Asm):
     a.label(l_skip)
 
 
-def kernel(variant: str = "") -> tuple[str, str]:
-    name = "toa_wgrad_nt_asm" + (f"_{variant}" if variant else "")
-    a = Asm(prefix="nt_" + (variant + "_" if variant else ""))
+def kernel() -> tuple[str, str]:
+    name = "toa_wgrad_nt_asm"
+    a = Asm(prefix="nt_")
     a.raw(f".globl {name}")
     a.raw(".p2align 8")
     a.raw(f".type {name},@function")
@@ -576,8 +569,7 @@ def kernel(variant: str = "") -> tuple[str, str]:
             a(ins)
     a(f"s_xor_b32 {sr(S_M0A)}, {sr(S_M0A)}, {sr(S_M0AT)}")
     a(f"s_xor_b32 {sr(S_M0B)}, {sr(S_M0B)}, {sr(S_M0BT)}")
-    if KNOBS["zero_late"]:
-        zero_acc(a)                             # under the first tiles' DMA flight
+    zero_acc(a)                                 # under the first tiles' DMA flight
     a("s_waitcnt vmcnt(16)")                    # own tile-0 pieces
     a("s_barrier")
     for j in range(8):

@@ -42,59 +42,35 @@ using namespace toa_shapes;
 #include "toa_asm_blob.inc"  // const unsigned char toa_asm_blob[]; size_t toa_asm_blob_len
 
 constexpr int kMaxDev = 64;
-enum { K_PLAIN = 0, K_SWIGLU_FWD = 1, K_SWIGLU_BWD = 2, K_PROBE = 3, K_TRACE = 4, K_TIMING = 5, K_TIMING2 = 6,
-       K_WGRAD = 7, K_V1 = 8, K_WGRAD_V1 = 16, K_ATTN_FWD = 17, K_ATTN_D1 = 18, K_ATTN_T1 = 23,
-       K_ATTN_DKDV = 26, K_DKDV_D1 = 27, K_DKDV_T1 = 34, K_SWIGLU_FWD_R4 = 41, K_SWIGLU_BWD_R4 = 42, K_SWBWD_V1 = 43, K_PLAIN_V9 = 48, K_DKDV_S7 = 49, K_DKDV_D8 = 50, K_DKDV_S8 = 51, K_SWFWD_P1 = 52, K_SWBWD_P1 = 53, K_ROPE = 54, K_DELTA = 55, K_RESADD = 56, K_N = 57 };
-// K_V1 .. K_N - 1: the A/B arms of the plain kernel (gemm_gen.py PLAIN_VARIANTS)
-const char* kNames[K_N] = {"toa_gemm_tn_asm_plain",    "toa_gemm_tn_asm_swiglu_fwd", "toa_gemm_tn_asm_swiglu_bwd",
-                           "toa_gemm_tn_asm_probe",    "toa_gemm_tn_asm_trace",      "toa_gemm_tn_asm_timing",
-                           "toa_gemm_tn_asm_timing2",  "toa_wgrad_nt_asm",           "toa_gemm_tn_asm_plain_v1",
-                           "toa_gemm_tn_asm_plain_v2", "toa_gemm_tn_asm_plain_v3", "toa_gemm_tn_asm_plain_v4",
-                           "toa_gemm_tn_asm_plain_v5", "toa_gemm_tn_asm_plain_v6", "toa_gemm_tn_asm_plain_v7",
-                           "toa_gemm_tn_asm_plain_v8", "toa_wgrad_nt_asm_v1",       "toa_attn_fwd_asm",
-                           // K_ATTN_D1 ..: attn_gen.py VARIANTS (diagnostic arms, wrong outputs by design)
-                           "toa_attn_fwd_asm_d1",      "toa_attn_fwd_asm_d2",        "toa_attn_fwd_asm_d3",
-                           "toa_attn_fwd_asm_d4",      "toa_attn_fwd_asm_d5",        "toa_attn_fwd_asm_t1",
-                           "toa_attn_fwd_asm_c1",      "toa_attn_fwd_asm_t2",        "toa_attn_dkdv_asm",
-                           // K_DKDV_D1 ..: attn_bwd_gen.py VARIANTS (diagnostic arms, wrong outputs by design)
-                           "toa_attn_dkdv_asm_d1",     "toa_attn_dkdv_asm_d2",       "toa_attn_dkdv_asm_d3",
-                           "toa_attn_dkdv_asm_d4",     "toa_attn_dkdv_asm_d5",       "toa_attn_dkdv_asm_d6",
-                           "toa_attn_dkdv_asm_d7",     "toa_attn_dkdv_asm_t1",
-                           // schedule-parameter arms (correct outputs)
-                           "toa_attn_dkdv_asm_s1",     "toa_attn_dkdv_asm_s2",       "toa_attn_dkdv_asm_s3",
-                           "toa_attn_dkdv_asm_s4",     "toa_attn_dkdv_asm_s5",       "toa_attn_dkdv_asm_s6",
-                           // the round-4 SwiGLU epilogues (drain per row block): in-model A/B arms
-                           "toa_gemm_tn_asm_swiglu_fwd_r4", "toa_gemm_tn_asm_swiglu_bwd_r4",
-                           // K_SWBWD_V1 ..: gemm_gen.py SWIGLU_BWD_VARIANTS (diagnostic arms, wrong outputs by design)
-                           "toa_gemm_tn_asm_swiglu_bwd_b1", "toa_gemm_tn_asm_swiglu_bwd_b2",
-                           "toa_gemm_tn_asm_swiglu_bwd_b3", "toa_gemm_tn_asm_swiglu_bwd_b4",
-                           "toa_gemm_tn_asm_swiglu_bwd_b5",
-                           // the plain kernel's ninth A/B arm (after the table above was laid out)
-                           "toa_gemm_tn_asm_plain_v9",
-                           // the dK/dV kernel's arm s7 (attn_bwd_gen.py VARIANTS, appended)
-                           "toa_attn_dkdv_asm_s7", "toa_attn_dkdv_asm_d8", "toa_attn_dkdv_asm_s8",
-                           // the persistent fused SwiGLU GEMMs (gemm_gen.py SWIGLU_PERSIST_VARIANTS)
-                           "toa_gemm_tn_asm_swiglu_fwd_p1", "toa_gemm_tn_asm_swiglu_bwd_p1",
-                           // the fused-QKV projection with RoPE + head-major relayout (gemm_gen.py epilogue_rope)
-                           "toa_gemm_tn_asm_rope",
-                           // the output projection's data gradient with the attention delta (epilogue_delta)
-                           "toa_gemm_tn_asm_delta",
-                           // C = X W^T + R (epilogue_resadd: the output projection's residual add)
-                           "toa_gemm_tn_asm_resadd"};
-
-// The NN-form kernels (gemm_gen.py kernel_nn: C = X W on W [K, N] as stored,
-// the data gradients without a transposed weight copy), a table of their own.
-enum { NN_PLAIN = 0, NN_SWIGLU_BWD = 1, NN_DELTA = 2, NN_N = 3 };
-const char* kNnNames[NN_N] = {"toa_gemm_nn_asm_plain", "toa_gemm_nn_asm_swiglu_bwd", "toa_gemm_nn_asm_delta"};
-
-constexpr int kNnBase = 1 << 16;  // get_fn / launch ids of the NN kernels: kNnBase + NN_*
+// Every kernel of the code object (gemm_gen.py generate()): member i of the
+// enum is name i of the array.  tests/test_asm_gemm.py checks the names
+// against the generated metadata.
+enum {
+  K_PLAIN, K_SWIGLU_FWD, K_SWIGLU_BWD, K_ROPE, K_DELTA, K_RESADD,   // TN epilogues (gemm_gen.py EPIS)
+  K_PLAIN_V3,                                                       // the persistent plain kernel (PLAIN_VARIANTS)
+  K_SWFWD_P1, K_SWBWD_P1,                                           // persistent fused SwiGLU (SWIGLU_PERSIST_VARIANTS)
+  K_WGRAD, K_ATTN_FWD, K_ATTN_T1,                                   // wgrad_gen.py; attn_gen.py and its timing arm
+  K_PROBE, K_TRACE, K_TIMING, K_TIMING2,                            // diagnostics of the plain kernel
+  K_ATTN_DKDV, K_DKDV_T1,                                           // attn_bwd_gen.py and its timing arm
+  K_NN_PLAIN, K_NN_SWIGLU_BWD, K_NN_DELTA,                          // NN form: C = X W on W [K, N] as stored (NN_EPIS)
+  K_N
+};
+const char* const kNames[] = {
+    "toa_gemm_tn_asm_plain",  "toa_gemm_tn_asm_swiglu_fwd", "toa_gemm_tn_asm_swiglu_bwd",
+    "toa_gemm_tn_asm_rope",   "toa_gemm_tn_asm_delta",      "toa_gemm_tn_asm_resadd",
+    "toa_gemm_tn_asm_plain_v3",
+    "toa_gemm_tn_asm_swiglu_fwd_p1", "toa_gemm_tn_asm_swiglu_bwd_p1",
+    "toa_wgrad_nt_asm",       "toa_attn_fwd_asm",           "toa_attn_fwd_asm_t1",
+    "toa_gemm_tn_asm_probe",  "toa_gemm_tn_asm_trace",      "toa_gemm_tn_asm_timing", "toa_gemm_tn_asm_timing2",
+    "toa_attn_dkdv_asm",      "toa_attn_dkdv_asm_t1",
+    "toa_gemm_nn_asm_plain",  "toa_gemm_nn_asm_swiglu_bwd", "toa_gemm_nn_asm_delta"};
+static_assert(sizeof(kNames) / sizeof(kNames[0]) == K_N, "one name per kernel id");
 
 struct DevModule {
   std::once_flag once;
   hipError_t err = hipSuccess;
   hipModule_t mod = nullptr;
   hipFunction_t fn[K_N] = {};
-  hipFunction_t nn[NN_N] = {};
 };
 DevModule g_mod[kMaxDev];
 
@@ -109,10 +85,9 @@ hipFunction_t get_fn(int which, hipError_t* err) {
   std::call_once(m.once, [&m]() {
     m.err = hipModuleLoadData(&m.mod, toa_asm_blob);
     for (int i = 0; m.err == hipSuccess && i < K_N; ++i) m.err = hipModuleGetFunction(&m.fn[i], m.mod, kNames[i]);
-    for (int i = 0; m.err == hipSuccess && i < NN_N; ++i) m.err = hipModuleGetFunction(&m.nn[i], m.mod, kNnNames[i]);
   });
   *err = m.err;
-  return m.err == hipSuccess ? (which >= kNnBase ? m.nn[which - kNnBase] : m.fn[which]) : nullptr;
+  return m.err == hipSuccess ? m.fn[which] : nullptr;
 }
 
 struct __attribute__((packed)) Args {
@@ -130,13 +105,7 @@ static_assert(sizeof(Args) == 96, "kernarg block must match csrc/asm/gemm_gen.py
 constexpr uint32_t kMapDefault = 2;  // groups of 4 row tiles walk the column tiles
 constexpr uint32_t kMapWalkCols = 16;
 
-// The plain kernel's A/B arms by variant number 1.. (gemm_gen.py
-// PLAIN_VARIANTS): kernel id, and whether it walks several tiles per
-// workgroup (SCHED "persist": its grid is one workgroup per CU).
-constexpr int kNumPlainVariants = 9;
-constexpr int kVariantFn[kNumPlainVariants] = {K_V1,     K_V1 + 1, K_V1 + 2, K_V1 + 3,  K_V1 + 4,
-                                               K_V1 + 5, K_V1 + 6, K_V1 + 7, K_PLAIN_V9};
-constexpr bool kVariantPersist[kNumPlainVariants] = {false, false, true, false, false, false, false, true, true};
+// The persistent kernels' grid: one workgroup per CU.
 constexpr unsigned kPersistGrid = 256;
 
 // First-wave start offsets per kernel family (plain / SwiGLU forward /
@@ -154,8 +123,8 @@ uint32_t phase_word(int which) {
     }
   });
   if (which == K_PLAIN) return g_phase[0];
-  if (which == K_SWIGLU_FWD || which == K_SWIGLU_FWD_R4) return g_phase[1];
-  if (which == K_SWIGLU_BWD || which == K_SWIGLU_BWD_R4) return g_phase[2];
+  if (which == K_SWIGLU_FWD) return g_phase[1];
+  if (which == K_SWIGLU_BWD) return g_phase[2];
   return 0;
 }
 
@@ -164,7 +133,7 @@ int launch(int which, const Args& a, hipStream_t stream, unsigned grid = 0) {
   hipFunction_t fn = get_fn(which, &err);
   if (!fn) return (int)err;
   Args k = a;
-  if (which != K_DELTA && which != kNnBase + NN_DELTA)   // (the delta kernels' bytes 88..95 are a pointer)
+  if (which != K_DELTA && which != K_NN_DELTA)   // (the delta kernels' bytes 88..95 are a pointer)
     k.phase = phase_word(which);
   size_t sz = sizeof(k);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
@@ -275,7 +244,7 @@ extern "C" int toa_gemm_shape_check(int form, const void* X, const void* W, cons
 }
 extern "C" const char* toa_gemm_shape_why(int reason) { return why(reason); }
 
-// Persistent plain kernel (PLAIN_VARIANTS v3: a workgroup per CU walks its
+// Persistent plain kernel (gemm_gen.py PLAIN_VARIANTS v3: a workgroup per CU walks its
 // tiles, the next tile's first k-tiles staged under the current epilogue).
 // In isolation it is 1.5-2.8 % faster at the qkv / o forward and data-gradient
 // forms (K <= 6144, N <= 6144; profiles/r6_defer), but in the model the step
@@ -298,7 +267,7 @@ static int gemm_asm_plain(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   if (M % 256 == 0 && use_persist(N, K)) {
     const unsigned tiles = a.tiles_m * a.tiles_n;
-    return launch(kVariantFn[2], a, stream, tiles < kPersistGrid ? tiles : kPersistGrid);
+    return launch(K_PLAIN_V3, a, stream, tiles < kPersistGrid ? tiles : kPersistGrid);
   }
   return launch(K_PLAIN, a, stream);
 }
@@ -320,20 +289,6 @@ extern "C" int toa_gemm_asm_set_persist(int v) {
   if (v < -1 || v > 1) return (int)hipErrorInvalidValue;
   g_persist = v;
   return 0;
-}
-
-// A/B: variant v of the plain kernel (0 = the product kernel, 1.. = the arms
-// gemm_gen.py PLAIN_VARIANTS lists), same arguments and checks as toa_gemm_asm.
-extern "C" int toa_gemm_asm_variant(int v, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* C,
-                                    int64_t ldc, int M, int N, int K, hipStream_t stream) {
-  if (v < 0 || v > kNumPlainVariants || (v == 9 && K < 192) || !takes(F_TN, operands(X, ldx, W, ldw, C, ldc, M, N, K)))
-    return (int)hipErrorInvalidValue;
-  Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
-  if (v > 0 && kVariantPersist[v - 1]) {
-    const unsigned tiles = a.tiles_m * a.tiles_n;
-    return launch(kVariantFn[v - 1], a, stream, tiles < kPersistGrid ? tiles : kPersistGrid);
-  }
-  return launch(v == 0 ? K_PLAIN : kVariantFn[v - 1], a, stream);
 }
 
 // A/B: the product kernel with an explicit tile order (kernarg `map`, see
@@ -437,9 +392,6 @@ extern "C" int toa_wgrad_asm_set_sumsq(float* sq) {
   return 0;
 }
 
-static int wgrad_asm_launch(int which, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C,
-                            int64_t ldc, float* W, int M, int N, int K, int split, int beta, hipStream_t stream);
-
 // Tile order of the weight-gradient kernel (wgrad_gen.py, the TN kernels'
 // map encoding), per shape from the in-process sweep of round 6
 // (profiles/r6_wmap; scripts/asm_gemm_bench.py --wgrad --wgrad-maps):
@@ -480,20 +432,6 @@ extern "C" int64_t toa_wgrad_asm_workspace(int M, int N, int K, int split) {
 
 extern "C" int toa_wgrad_asm(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C, int64_t ldc,
                              float* W, int M, int N, int K, int split, int beta, hipStream_t stream) {
-  return wgrad_asm_launch(K_WGRAD, A, lda, B, ldb, C, ldc, W, M, N, K, split, beta, stream);
-}
-
-// A/B: variant v of the weight-gradient kernel (0 = product, 1 = the round-4
-// schedule: "spread" slot map, accumulators zeroed before the prologue DMA).
-extern "C" int toa_wgrad_asm_variant(int v, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C,
-                                     int64_t ldc, float* W, int M, int N, int K, int split, int beta,
-                                     hipStream_t stream) {
-  if (v < 0 || v > 1) return (int)hipErrorInvalidValue;
-  return wgrad_asm_launch(v ? K_WGRAD_V1 : K_WGRAD, A, lda, B, ldb, C, ldc, W, M, N, K, split, beta, stream);
-}
-
-static int wgrad_asm_launch(int which, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C,
-                            int64_t ldc, float* W, int M, int N, int K, int split, int beta, hipStream_t stream) {
   Operands o = operands(A, lda, B, ldb, C, ldc, M, N, K, W);
   o.split = split;
   WgradPlan plan;
@@ -523,7 +461,7 @@ static int wgrad_asm_launch(int which, const bf16_t* A, int64_t lda, const bf16_
   g_wgrad_sq = nullptr;
   memcpy(&a.phase, &sq, sizeof(sq));   // bytes 88..95: wgrad_gen.py KARG "sq"
   hipError_t err;
-  hipFunction_t fn = get_fn(which, &err);
+  hipFunction_t fn = get_fn(K_WGRAD, &err);
   if (!fn) return (int)err;
   size_t sz = sizeof(a);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
@@ -557,27 +495,15 @@ extern "C" int toa_attn_fwd_asm(const bf16_t* q, const bf16_t* k, const bf16_t* 
   return attn_fwd_asm_launch(K_ATTN_FWD, q, k, v, o, lse, B, H, Hk, S, D, flags, scale, stream);
 }
 
-// Diagnostic: arm v (1.. = attn_gen.py VARIANTS, 0 = the product kernel),
-// same contract; the arms' outputs are wrong by design (timing only).
-extern "C" int toa_attn_fwd_asm_variant(int v, const bf16_t* q, const bf16_t* k, const bf16_t* v_, bf16_t* o,
-                                        float* lse, int B, int H, int Hk, int S, int D, int flags, float scale,
-                                        hipStream_t stream) {
-  if (v < 0 || v > K_ATTN_DKDV - K_ATTN_D1 || K_ATTN_D1 + v - 1 == K_ATTN_T1 || K_ATTN_D1 + v - 1 == K_ATTN_DKDV - 1)
-    return (int)hipErrorInvalidValue;  // the timing arms take toa_attn_fwd_asm_timing
-  return attn_fwd_asm_launch(v ? K_ATTN_D1 + v - 1 : K_ATTN_FWD, q, k, v_, o, lse, B, H, Hk, S, D, flags, scale,
-                             stream);
-}
-
 // Diagnostic: the product kernel with s_memtime stamps (attn_gen.py
 // timing_store): 8 dwords per (workgroup, wave) at dbg + 32 (4 wg + wave) --
 // prologue / loop / epilogue shader cycles, tiles, query block, rescales.
-// which = 1: the product schedule's timing arm, 2: the group-placed one's.
+// which = 1 (the one timing arm; the argument keeps the entry's signature).
 extern "C" int toa_attn_fwd_asm_timing(int which, void* dbg, const bf16_t* q, const bf16_t* k, const bf16_t* v,
                                        bf16_t* o, float* lse, int B, int H, int Hk, int S, int D, int flags,
                                        float scale, hipStream_t stream) {
-  if (!dbg || !al16(dbg) || (which != 1 && which != 2)) return (int)hipErrorInvalidValue;
-  return attn_fwd_asm_launch(which == 1 ? K_ATTN_T1 : K_ATTN_DKDV - 1, q, k, v, o, lse, B, H, Hk, S, D, flags, scale, stream,
-                             dbg);
+  if (!dbg || !al16(dbg) || which != 1) return (int)hipErrorInvalidValue;
+  return attn_fwd_asm_launch(K_ATTN_T1, q, k, v, o, lse, B, H, Hk, S, D, flags, scale, stream, dbg);
 }
 
 static int attn_fwd_asm_launch(int which, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse,
@@ -616,16 +542,6 @@ static int attn_fwd_asm_launch(int which, const bf16_t* q, const bf16_t* k, cons
   return (int)hipModuleLaunchKernel(fn, (unsigned)nwg, 1, 1, 256, 1, 1, 0, stream, nullptr, cfg);
 }
 
-// In-model A/B (scripts/wgrad_inmodel_ab.py epi=r4): 1 = the fused SwiGLU
-// GEMMs run the round-4 epilogues (every row block drained); 0 = the
-// software-pipelined ones (csrc/asm/gemm_gen.py epilogue_swiglu_bwd_pipe).
-static int g_epi_r4 = 0;
-extern "C" int toa_gemm_asm_set_epi_variant(int v) {
-  if (v < 0 || v > 1) return (int)hipErrorInvalidValue;
-  g_epi_r4 = v;
-  return 0;
-}
-
 // Persistent fused SwiGLU GEMMs (gemm_gen.py SWIGLU_PERSIST_VARIANTS: a
 // workgroup per CU walks its tiles, the next tile's first k-tiles staged
 // before the current tile's epilogue).  bit 0: the forward, bit 1: the
@@ -644,7 +560,7 @@ extern "C" int toa_gemm_asm_set_swiglu_persist(int v) {
   return 0;
 }
 static int launch_swiglu(int which, int persist_bit, const Args& a, hipStream_t stream) {
-  if (!g_epi_r4 && a.m == 0 && (swiglu_persist() & persist_bit)) {   // (the persistent arms: whole tiles only)
+  if (a.m == 0 && (swiglu_persist() & persist_bit)) {   // (the persistent arms: whole tiles only)
     const unsigned tiles = a.tiles_m * a.tiles_n;
     return launch(which == K_SWIGLU_FWD ? K_SWFWD_P1 : K_SWBWD_P1, a, stream,
                   tiles < kPersistGrid ? tiles : kPersistGrid);
@@ -660,7 +576,7 @@ extern "C" int toa_gemm_asm_swiglu(const bf16_t* X, int64_t ldx, const bf16_t* W
   a.lds = (uint32_t)(lds_ * 2);
   a.fw = (uint32_t)((int64_t)F * ldw * 2);
   a.fc = (uint32_t)(F * 2);
-  return g_epi_r4 && a.m == 0 ? launch(K_SWIGLU_FWD_R4, a, stream) : launch_swiglu(K_SWIGLU_FWD, 1, a, stream);
+  return launch_swiglu(K_SWIGLU_FWD, 1, a, stream);
 }
 
 extern "C" int toa_gemm_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16_t* WdT, int64_t ldw,
@@ -672,7 +588,7 @@ extern "C" int toa_gemm_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const bf16
   a.S = (uint64_t)GU;
   a.lds = (uint32_t)(ldgu * 2);
   a.fc = (uint32_t)(F * 2);
-  return g_epi_r4 && a.m == 0 ? launch(K_SWIGLU_BWD_R4, a, stream) : launch_swiglu(K_SWIGLU_BWD, 2, a, stream);
+  return launch_swiglu(K_SWIGLU_BWD, 2, a, stream);
 }
 
 // The fused-QKV projection x Wqkv^T written as RoPE-rotated, head-major
@@ -717,7 +633,7 @@ extern "C" int toa_gemm_nn_asm(const bf16_t* X, int64_t ldx, const bf16_t* W, in
                                int M, int N, int K, hipStream_t stream) {
   if (!takes(F_NN, operands(X, ldx, W, ldw, C, ldc, M, N, K))) return (int)hipErrorInvalidValue;
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
-  return launch(kNnBase + NN_PLAIN, a, stream);
+  return launch(K_NN_PLAIN, a, stream);
 }
 
 // toa_gemm_asm_swiglu_bwd on Wd [K = D, F] as stored: dgu = SwiGLU'(gu) applied to ds = dY Wd.
@@ -730,7 +646,7 @@ extern "C" int toa_gemm_nn_asm_swiglu_bwd(const bf16_t* dY, int64_t ldy, const b
   a.S = (uint64_t)GU;
   a.lds = (uint32_t)(ldgu * 2);
   a.fc = (uint32_t)(F * 2);
-  return launch(kNnBase + NN_SWIGLU_BWD, a, stream);
+  return launch(K_NN_SWIGLU_BWD, a, stream);
 }
 
 // toa_gemm_asm_delta on Wo [K, N] as stored: dX = dY Wo with the attention
@@ -745,7 +661,7 @@ extern "C" int toa_gemm_nn_asm_delta(const bf16_t* X, int64_t ldx, const bf16_t*
   a.fw = (uint32_t)S;
   a.fc = (uint32_t)H;
   memcpy(&a.phase, &ndelta, sizeof(ndelta));   // bytes 88..95
-  return launch(kNnBase + NN_DELTA, a, stream);
+  return launch(K_NN_DELTA, a, stream);
 }
 
 // C = X W^T + R, R bf16 laid out like C (gemm_gen.py epilogue_resadd).
@@ -755,22 +671,6 @@ extern "C" int toa_gemm_asm_resadd(const bf16_t* X, int64_t ldx, const bf16_t* W
   Args a = base_args(X, ldx, W, ldw, C, ldc, M, N / 256, K);
   a.S = (uint64_t)R;
   return launch(K_RESADD, a, stream);
-}
-
-// DIAGNOSTIC: arm v (1..) of the fused SwiGLU backward (gemm_gen.py
-// SWIGLU_BWD_VARIANTS: the main loop alone, no loads, no math, no stores),
-// same arguments and checks as toa_gemm_asm_swiglu_bwd; v = 0 the product.
-extern "C" int toa_gemm_asm_swiglu_bwd_variant(int v, const bf16_t* dY, int64_t ldy, const bf16_t* WdT, int64_t ldw,
-                                               const bf16_t* GU, int64_t ldgu, bf16_t* dGU, int64_t lddgu, int M,
-                                               int F, int K, hipStream_t stream) {
-  if (v < 0 || v > K_PLAIN_V9 - K_SWBWD_V1 || M % 256 ||   // (the arms: whole tiles only)
-      !takes(F_TN_SWIGLU_BWD, operands(dY, ldy, WdT, ldw, dGU, lddgu, M, F, K, GU, ldgu)))
-    return (int)hipErrorInvalidValue;
-  Args a = base_args(dY, ldy, WdT, ldw, dGU, lddgu, M, F / 256, K);
-  a.S = (uint64_t)GU;
-  a.lds = (uint32_t)(ldgu * 2);
-  a.fc = (uint32_t)(F * 2);
-  return launch(v == 0 ? K_SWIGLU_BWD : K_SWBWD_V1 + v - 1, a, stream);
 }
 
 // Causal flash-attention dK / dV backward of the dS form (csrc/asm/attn_bwd_gen.py),
@@ -794,36 +694,12 @@ static int attn_dkdv_launch(int which, const bf16_t* q, const bf16_t* k, const b
                             int Hk, int S, int D, float scale, int flags, const float* cosv, const float* sinv, int H3,
                             hipStream_t stream, void* dbg = nullptr);
 
-// In-model A/B: toa_attn_dkdv_asm_set_arm(1) runs the packed-VALU arm (s7,
-// the round-5 form) in place of the product kernel; 0 = the product.
-static int g_dkdv_arm = 0;
-extern "C" int toa_attn_dkdv_asm_set_arm(int v) {
-  if (v < 0 || v > 1) return (int)hipErrorInvalidValue;
-  g_dkdv_arm = v;
-  return 0;
-}
-
 extern "C" int toa_attn_dkdv_asm(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* dout,
                                  const float* nlse2, const float* ndelta, bf16_t* dk, bf16_t* dv, bf16_t* ds, int B,
                                  int H, int Hk, int S, int D, float scale, int flags, const float* cosv,
                                  const float* sinv, int H3, hipStream_t stream) {
-  return attn_dkdv_launch(g_dkdv_arm ? K_DKDV_S7 : K_ATTN_DKDV, q, k, v, dout, nlse2, ndelta, dk, dv, ds, B, H, Hk, S,
-                          D, scale, flags, cosv, sinv, H3, stream);
-}
-
-// Diagnostic: arm v (1.. = attn_bwd_gen.py VARIANTS, 0 = the product kernel),
-// same contract; the arms' outputs are wrong by design (timing only).
-extern "C" int toa_attn_dkdv_asm_variant(int v, const bf16_t* q, const bf16_t* k, const bf16_t* v_,
-                                         const bf16_t* dout, const float* nlse2, const float* ndelta, bf16_t* dk,
-                                         bf16_t* dv, bf16_t* ds, int B, int H, int Hk, int S, int D, float scale,
-                                         int flags, const float* cosv, const float* sinv, int H3, hipStream_t stream) {
-  // arms 1..14 sit at K_DKDV_D1.., arms 15.. (s7, d8, s8) were appended from K_DKDV_S7
-  constexpr int kDkdvArms = K_SWIGLU_FWD_R4 - K_DKDV_D1;
-  if (v < 0 || v > kDkdvArms + (K_DKDV_S8 - K_DKDV_S7 + 1) || (v && v <= kDkdvArms && K_DKDV_D1 + v - 1 == K_DKDV_T1))
-    return (int)hipErrorInvalidValue;  // the timing arm takes its own entry
-  const int which = v == 0 ? K_ATTN_DKDV : (v <= kDkdvArms ? K_DKDV_D1 + v - 1 : K_DKDV_S7 + v - kDkdvArms - 1);
-  return attn_dkdv_launch(which, q, k, v_, dout, nlse2, ndelta, dk, dv, ds, B, H, Hk, S, D, scale, flags, cosv, sinv,
-                          H3, stream);
+  return attn_dkdv_launch(K_ATTN_DKDV, q, k, v, dout, nlse2, ndelta, dk, dv, ds, B, H, Hk, S, D, scale, flags, cosv,
+                          sinv, H3, stream);
 }
 
 // Diagnostic: the product kernel with s_memtime stamps (attn_bwd_gen.py

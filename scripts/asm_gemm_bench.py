@@ -3,11 +3,10 @@ the Llama-3-8B forward / data-gradient forms, in-process interleaved rounds on
 random operands (guide section 5.4 rules 24/25).
 
     python scripts/asm_gemm_bench.py --check        # numerics only (small shapes)
-    python scripts/asm_gemm_bench.py [--tokens 24576] [--rounds 5] [--reps 5] [--variants 1,2,3]
+    python scripts/asm_gemm_bench.py [--tokens 24576] [--rounds 5] [--reps 5]
 
 Arms: asm (toa_gemm_asm), blt_nosk (hipBLASLt non-stream-K table),
-blt_heur (torch.matmul), asm_v<n> (the plain kernel's A/B arms,
-gemm_gen.py PLAIN_VARIANTS; checked bit-identical to asm), and the fused MLP
+blt_heur (torch.matmul), and the fused MLP
 ends (asm SwiGLU epilogues vs hipBLASLt + the SwiGLU row kernels).
 """
 import argparse
@@ -58,19 +57,6 @@ def with_phase(kind, word, fn):
         return fn()
     finally:
         _lib.call("toa_gemm_asm_set_phase", kind, 0)
-
-
-def asm_swiglu_bwd_variant(v, d2, wdt, gu, dgu):
-    M, F = d2.shape[0], wdt.shape[0]
-    _lib.call("toa_gemm_asm_swiglu_bwd_variant", v, _lib.ptr(d2), d2.stride(0), _lib.ptr(wdt), wdt.stride(0),
-              _lib.ptr(gu), 2 * F, _lib.ptr(dgu), 2 * F, M, F, d2.shape[1], _lib.stream(d2))
-
-
-def asm_variant(v, x, w, y):
-    M, K = x.shape
-    N = w.shape[0]
-    _lib.call("toa_gemm_asm_variant", v, _lib.ptr(x), x.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(y), y.stride(0),
-              M, N, K, _lib.stream(x))
 
 
 def asm_map(tmap, x, w, y):
@@ -229,7 +215,7 @@ def timing(a):
             r2 = rec.cpu().numpy().view(np.uint32).reshape(nwg, 4, 8).astype(np.float64)
             loops = np.maximum(r2[:, :, 5] - 2, 1)  # main-loop iterations (the two tail tiles carry no DMA)
             import gemm_gen  # csrc/asm: the product slot map's stretch lengths
-            nm = gemm_gen.span_mfmas(gemm_gen.SLOT_MAPS[gemm_gen.SCHED["map"]])
+            nm = gemm_gen.span_mfmas(gemm_gen.SLOT_MAP)
             spans = dict(zip(("xdma_cyc_per_mfma", "wdma_pre_wait_cyc_per_mfma", "wdma_post_wait_cyc_per_mfma"), nm))
             sp = {k: round(float((r2[:, :, i] / loops).mean() / n), 2) for i, (k, n) in enumerate(spans.items())}
             for _ in range(3):
@@ -281,13 +267,7 @@ def wgrad(a):
             _lib.call("toa_wgrad_asm", _lib.ptr(dy), N, _lib.ptr(x), K, _lib.ptr(g), K, _lib.ptr(ws), N, K, T, 0, 0,
                       _lib.stream(dy))
 
-        g3 = torch.empty_like(g)
-
-        def asm_v1():  # the round-4 schedule of the same kernel
-            _lib.call("toa_wgrad_asm_variant", 1, _lib.ptr(dy), N, _lib.ptr(x), K, _lib.ptr(g3), K, _lib.ptr(ws), N,
-                      K, T, 0, 0, _lib.stream(dy))
-
-        arms = [("asm", asm_), ("asm_v1", asm_v1), ("hip", hip), ("blt", lambda: torch.mm(dy.t(), x))]
+        arms = [("asm", asm_), ("hip", hip), ("blt", lambda: torch.mm(dy.t(), x))]
         g4 = torch.empty_like(g)
 
         def mapped(tm_):   # the product kernel with another tile order (toa_wgrad_asm_set_map)
@@ -324,9 +304,6 @@ def wgrad(a):
         rec = {k: {"ms": round(statistics.median(v), 4), "TFps": round(fl / statistics.median(v) / 1e9, 1)}
                for k, v in ts.items()}
         rec["asm_vs_hip_rel"] = round(rel(g, g2), 6)
-        asm_v1()
-        torch.cuda.synchronize()
-        rec["asm_v1_bit_identical"] = bool(torch.equal(g, g3))
         for tm_ in wmaps:
             mapped(tm_)
             torch.cuda.synchronize()
@@ -398,7 +375,6 @@ def bench(a):
     T = a.tokens
     torch.manual_seed(0)
     out = {"tokens": T, "forms": {}}
-    variants = [int(v) for v in a.variants.split(",") if v]
     maps = [int(v) for v in a.maps.split(",") if v]
     phases = [int(v, 0) for v in a.phases.split(",") if v]
     for name, (K, N) in FORMS.items():
@@ -412,8 +388,6 @@ def bench(a):
                     ("blt_nosk", lambda: (gemm.set_mode("nosk"), gemm.linear_fwd(x, w))),
                     ("blt_heur", lambda: torch.matmul(x, w.t()))]
             yv = torch.empty_like(y)
-            for v in variants:
-                arms.append((f"asm_v{v}", lambda v=v: asm_variant(v, x, w, yv)))
             for tm_ in maps:
                 arms.append((f"asm_map{tm_}", lambda tm_=tm_: asm_map(tm_, x, w, yv)))
             for ph in phases:
@@ -424,9 +398,6 @@ def bench(a):
                     ts[k].append(timer(f, a.reps))
             asm(x, w, y)
             same = {}
-            for v in variants:
-                asm_variant(v, x, w, yv)
-                same[f"asm_v{v}"] = bool(torch.equal(y, yv))
             for tm_ in maps:
                 asm_map(tm_, x, w, yv)
                 same[f"asm_map{tm_}"] = bool(torch.equal(y, yv))
@@ -455,7 +426,6 @@ def bench(a):
                 ("blt_unfused_fwd", lambda: (gemm.set_mode("nosk"), llm.swiglu(gemm.linear_fwd(x, wgu)))),
                 ("asm_fused_bwd", lambda: asm_swiglu_bwd(d2, wdt, gu)),
                 ("blt_unfused_bwd", lambda: (gemm.set_mode("nosk"), llm.swiglu_bwd(gemm.linear_fwd(d2, wdt), gu)))]
-        dgu_v = torch.empty_like(gu)
 
         def mapped(tm_, fn):
             _lib.call("toa_gemm_asm_set_map", tm_)
@@ -467,8 +437,6 @@ def bench(a):
         for tm_ in maps:
             arms += [(f"asm_fused_fwd_map{tm_}", lambda tm_=tm_: mapped(tm_, lambda: asm_swiglu(x, wgu))),
                      (f"asm_fused_bwd_map{tm_}", lambda tm_=tm_: mapped(tm_, lambda: asm_swiglu_bwd(d2, wdt, gu)))]
-        for v in [int(t) for t in a.swiglu_variants.split(",") if t]:
-            arms.append((f"asm_fused_bwd_b{v}", lambda v=v: asm_swiglu_bwd_variant(v, d2, wdt, gu, dgu_v)))
         def persistent(bit, fn):
             _lib.call("toa_gemm_asm_set_swiglu_persist", bit)
             try:
@@ -515,10 +483,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--forms", default="")
     ap.add_argument("--mlp", type=int, default=1)
-    ap.add_argument("--variants", default="", help="plain-kernel A/B arms to add, e.g. 1,2,3")
     ap.add_argument("--maps", default="", help="tile orders to add as arms (kernarg map words, e.g. 2,3,18,20)")
-    ap.add_argument("--swiglu-variants", default="", help="fused SwiGLU backward diagnostic arms (1..5) "
-                                                          "added to the MLP arms (gemm_gen.SWIGLU_BWD_VARIANTS)")
     ap.add_argument("--swiglu-persist", action="store_true", help="add the persistent fused SwiGLU arms (p1)")
     ap.add_argument("--phases", default="", help="first-wave start-offset words to add as arms (n | log2 g << 16, "
                                                  "e.g. 0x10028,0x20014): plain forms and the fused MLP")

@@ -1,10 +1,10 @@
 """In-process timing of the assembly dK/dV kernel (csrc/asm/attn_bwd_gen.py)
-and its diagnostic arms at the Llama-3-8B bench shape (B=6, H=32, Hkv=8,
-S=4096, D=128, dO in [B,S,H,D], RoPE epilogue into d(qkv) rows), interleaved
-rounds on random data.  Arm v (1..) switches one mechanism off (VARIANTS in
-the generator); its output is wrong by design, only its time is read.
+at the Llama-3-8B bench shape (B=6, H=32, Hkv=8, S=4096, D=128, dO in
+[B,S,H,D], RoPE epilogue into d(qkv) rows) on random data: its wall time, and
+the loop cycles per step from its s_memtime arm (VARIANTS "t1").  (The arms
+that switched one mechanism off each are pruned: docs/kernels.md.)
 
-    python scripts/attn_dkdv_arms.py [--rounds 5] [--reps 5] [--arms 0,1,2,3,4,5,6]
+    python scripts/attn_dkdv_arms.py [--rounds 5] [--reps 5]
 """
 import argparse
 import json
@@ -15,7 +15,6 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-sys.path.insert(0, "csrc/asm")
 from tf_operator_amd.ops import _lib  # noqa: E402
 
 
@@ -24,10 +23,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=6)
-    ap.add_argument("--arms", default="0,1,2,3,4,5,6")
     a = ap.parse_args()
-    import attn_bwd_gen
-    names = ["asm"] + [v for v, _ in attn_bwd_gen.VARIANTS]
     B, H, Hk, S, D = a.batch, 32, 8, 4096, 128
     H3 = H + 2 * Hk
     dev = "cuda"
@@ -56,28 +52,25 @@ def main():
     ds_bytes = B * H * (nb * (nb + 1) // 2) * 2048
     nlse2 = ws[ds_bytes:ds_bytes + B * H * S * 4]
 
-    def run(arm):
-        _lib.call("toa_attn_dkdv_asm_variant", arm, P(q), P(k), P(v), P(do), P(nlse2), P(delta), P(dqkv), P(dqkv),
+    def run():
+        _lib.call("toa_attn_dkdv_asm", P(q), P(k), P(v), P(do), P(nlse2), P(delta), P(dqkv), P(dqkv),
                   P(ws), B, H, Hk, S, D, scale, 3, P(cosv), P(sinv), H3, st)
 
-    arms = [int(x) for x in a.arms.replace("+", ",").split(",")]
     # flops of dK/dV: S, dP, dV, dK over the causal half (4 S^2 D products x 2 flop / 2)
     flops = 4 * B * H * S * S * D
-    times = {x: [] for x in arms}
+    times = []
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     for _ in range(a.rounds):
-        for x in arms:
-            run(x)
-            ev[0].record()
-            for _ in range(a.reps):
-                run(x)
-            ev[1].record()
-            torch.cuda.synchronize()
-            times[x].append(ev[0].elapsed_time(ev[1]) / a.reps)
-    res = {"shape": [B, H, Hk, S, D]}
-    for x, t in times.items():
-        med = statistics.median(t)
-        res[names[x]] = {"median_ms": round(med, 4), "min_ms": round(min(t), 4), "PFps": round(flops / med / 1e12, 3)}
+        run()
+        ev[0].record()
+        for _ in range(a.reps):
+            run()
+        ev[1].record()
+        torch.cuda.synchronize()
+        times.append(ev[0].elapsed_time(ev[1]) / a.reps)
+    med = statistics.median(times)
+    res = {"shape": [B, H, Hk, S, D],
+           "asm": {"median_ms": round(med, 4), "min_ms": round(min(times), 4), "PFps": round(flops / med / 1e12, 3)}}
     # the s_memtime arm: loop cycles per step (64 MFMAs = 2048 matrix-core cycles per SIMD)
     nwg = (S // 128) * B * Hk
     dbg = torch.zeros(nwg * 4 * 8, device=dev, dtype=torch.int32)

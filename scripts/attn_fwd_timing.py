@@ -25,7 +25,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=6)
     ap.add_argument("--seq", type=int, default=4096)
-    ap.add_argument("--arm", type=int, default=1, help="1: product schedule, 2: group-placed fillers (c1)")
     a = ap.parse_args()
     B, H, Hk, S, D = a.batch, 32, 8, a.seq, 128
     torch.manual_seed(0)
@@ -40,17 +39,16 @@ def main():
     dbg = torch.zeros(nwg * 4 * 8, device="cuda", dtype=torch.int32)
     P, st = _lib.ptr, _lib.stream(q)
     args = (B, H, Hk, S, D, 3, 1.0 / math.sqrt(D), st)
-    var = 0 if a.arm == 1 else 7   # the product kernel / its c1 arm (attn_gen.py VARIANTS index)
     for _ in range(3):
-        _lib.call("toa_attn_fwd_asm_variant", var, P(q), P(k), P(v), P(o), P(lse), *args)
+        _lib.call("toa_attn_fwd_asm", P(q), P(k), P(v), P(o), P(lse), *args)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     ev[0].record()
     for _ in range(10):
-        _lib.call("toa_attn_fwd_asm_variant", var, P(q), P(k), P(v), P(o), P(lse), *args)
+        _lib.call("toa_attn_fwd_asm", P(q), P(k), P(v), P(o), P(lse), *args)
     ev[1].record()
     torch.cuda.synchronize()
     wall_us = ev[0].elapsed_time(ev[1]) / 10 * 1e3
-    _lib.call("toa_attn_fwd_asm_timing", a.arm, P(dbg), P(q), P(k), P(v), P(o2), P(lse2), *args)
+    _lib.call("toa_attn_fwd_asm_timing", 1, P(dbg), P(q), P(k), P(v), P(o2), P(lse2), *args)
     torch.cuda.synchronize()
     rec = dbg.view(nwg, 4, 8).cpu().numpy().astype(np.int64)
     pro, loop, epi, tiles, qb, resc = (rec[..., i] for i in range(6))

@@ -4,10 +4,9 @@ process (one model, one set of buffers): alternating timed windows of
 
     python scripts/wgrad_inmodel_ab.py [--rounds 3] [--steps 4] [--arms wgrad=asm+gemm=nosk,wgrad=hip+gemm=nosk]
 
-An arm is settings joined by '+': wgrad=asm|hip|asm_v1 (ops.gemm.set_wgrad_kernel),
+An arm is settings joined by '+': wgrad=asm|hip (ops.gemm.set_wgrad_kernel),
 gemm=asm|nosk (ops.gemm.set_mode: forward / data-gradient policy), attnf=N /
 attnb=N / attnd=N (toa_attn_set_fwd_variant / _bwd_variant / _dkdv_variant forms),
-epi=r4|pipe (the fused SwiGLU GEMMs' epilogues, toa_gemm_asm_set_epi_variant),
 wmap=N (the weight-gradient tile order, toa_wgrad_asm_set_map; -1 = the per-shape rule),
 persist=N (the plain TN kernel's persistent form, toa_gemm_asm_set_persist; -1 = the per-shape rule),
 swp=N (the fused SwiGLU GEMMs' persistent forms, toa_gemm_asm_set_swiglu_persist: bit 0 fwd, bit 1 bwd),
@@ -23,9 +22,8 @@ adamcap=N (the flat AdamW grid cap / 1024, toa_set_stream_variant),
 dgrad=wt|nn (the data gradients on the W^T copies, or on W as stored through the NN-form kernels: the weights'
 ``_toa_wt`` views are hidden for the window; the copies stay built and refreshed in both arms, so the arms differ by
 the GEMM form alone, not by the refresh pass or the memory the copies take),
-or the presets r4 (every round-4 default kernel: nosk GEMMs, the round-4
-weight-gradient schedule, the HIP attention forward and dK/dV) and head
-(this tree's defaults).  Same-process windows remove the box-to-box spread
+or the presets r4 (the round-4 choices still selectable: nosk GEMMs, the HIP
+attention forward and dK/dV) and head (this tree's defaults).  Same-process windows remove the box-to-box spread
 (about +-2.5 %) from the comparison:
 
     python scripts/wgrad_inmodel_ab.py --arms r4,head --rounds 8
@@ -48,8 +46,8 @@ TR = None   # the trainer (arms that switch trainer state: ovl)
 
 def apply(arm: str):
     """arm: settings joined by '+', e.g. wgrad=hip+gemm=nosk."""
-    presets = {"r4": "gemm=nosk+wgrad=asm_v1+attnf=1+attnd=0+epi=r4",
-               "head": "gemm=asm+wgrad=asm+attnf=-1+attnd=-1+epi=pipe"}
+    presets = {"r4": "gemm=nosk+wgrad=asm+attnf=1+attnd=0",
+               "head": "gemm=asm+wgrad=asm+attnf=-1+attnd=-1"}
     arm = presets.get(arm, arm)
     for part in arm.split("+"):
         key, val = part.split("=")
@@ -63,10 +61,6 @@ def apply(arm: str):
             _lib.call("toa_attn_set_bwd_variant", int(val))
         elif key == "attnd":
             _lib.call("toa_attn_set_dkdv_variant", int(val))
-        elif key == "epi":   # the fused SwiGLU GEMMs' epilogues: r4 (drained per row block) or pipe
-            _lib.call("toa_gemm_asm_set_epi_variant", 1 if val == "r4" else 0)
-        elif key == "dkpk":   # the assembly dK/dV with round 5's packed P / dS VALU (1) or the scalar product (0)
-            _lib.call("toa_attn_dkdv_asm_set_arm", int(val))
         elif key == "persist":   # TN plain kernel: -1 = the per-shape rule, 0 = never persistent, 1 = always
             _lib.call("toa_gemm_asm_set_persist", int(val))
         elif key == "swp":   # fused SwiGLU GEMMs persistent: bit 0 forward, bit 1 backward

@@ -142,12 +142,10 @@ def check(r, S):
     assert err < 1e-2 * max(1.0, np.abs(ref).max()), f"dS max err {err}"
 
 
-def expected_drops(B, H, Hk, S, per_block=None):
+def expected_drops(B, H, Hk, S, per_block=4):
     """Stores of blocks wholly above the diagonal: per (kv head, query head,
-    key block kb) step mod < 2, half m, wave w with 2 mod + m < w -- two
-    16-B stores each (four 8-B ones in round 5's form, arm s8)."""
-    if per_block is None:
-        per_block = 2 if attn_bwd_gen.KNOBS["dswide"] else 4
+    key block kb) step mod < 2, half m, wave w with 2 mod + m < w -- four
+    8-B stores each."""
     rep = H // Hk
     per = sum(1 for mod in range(2) for m in range(2) for w in range(4) if 2 * mod + m < w)
     return per_block * per * B * Hk * rep * (S // 128)
@@ -192,29 +190,3 @@ def test_dkdv_s512_two_kv_heads():
     B, H, Hk, S = 1, 4, 2, 512
     r = run(rnd((B, H, S, 128), 13), rnd((B, Hk, S, 128), 14), rnd((B, Hk, S, 128), 15), rnd((B, H, S, 128), 16))
     check(r, S)
-
-
-def test_dkdv_packed_valu_arm_matches():
-    """Arm s7 (round 5's P / dS on packed v_pk_fma_f32 / v_pk_mul_f32 pairs;
-    the product kernel now uses scalar ops): the same dK / dV / dS to fp64
-    tolerance, the diagonal blocks' stores dropped the same way."""
-    knobs = dict(attn_bwd_gen.VARIANTS)["s7"]
-    text = attn_bwd_gen.generate([attn_bwd_gen.variant_kernel("s7", knobs)])
-    B, H, Hk, S = 1, 2, 1, 256
-    r = run(rnd((B, H, S, 128), 5), rnd((B, Hk, S, 128), 6), rnd((B, Hk, S, 128), 7), rnd((B, H, S, 128), 8),
-            bshd=True, text=text, name=attn_bwd_gen.NAME + "_s7")
-    check(r, S)
-    assert r["dropped"] == expected_drops(B, H, Hk, S)   # (s7 keeps the 16-B stores)
-
-
-def test_dkdv_wide_store_arm_matches():
-    """Arm s8 (two 16-B dS stores per block built by permlane32 swaps instead
-    of the product's four 8-B ones; the barrier's vmcnt counts two): the same
-    outputs under the strict-VMEM emulator, two drops per block."""
-    knobs = dict(attn_bwd_gen.VARIANTS)["s8"]
-    text = attn_bwd_gen.generate([attn_bwd_gen.variant_kernel("s8", knobs)])
-    B, H, Hk, S = 1, 2, 1, 256
-    r = run(rnd((B, H, S, 128), 5), rnd((B, Hk, S, 128), 6), rnd((B, Hk, S, 128), 7), rnd((B, H, S, 128), 8),
-            bshd=True, text=text, name=attn_bwd_gen.NAME + "_s8")
-    check(r, S)
-    assert r["dropped"] == expected_drops(B, H, Hk, S, per_block=2)

@@ -60,10 +60,10 @@ def test_asm_gemm_plain_emulated(M, N, K):
     assert np.mean(np.abs(C - tof(bf16(ref))) <= np.abs(ref) * 2 ** -7) > 0.999
 
 
-@pytest.mark.parametrize("variant", [v for v, k in gemm_gen.PLAIN_VARIANTS if not k.get("diag")])
+@pytest.mark.parametrize("variant", ["v3"])
 def test_asm_gemm_variants_match_product_kernel(variant):
-    """Each A/B arm of the plain kernel (other LDS pad, DMA spacing, wait slot,
-    row-group size) writes exactly the product kernel's C on a 5 x 2 grid."""
+    """The persistent arm of the plain kernel writes exactly the product
+    kernel's C on a 5 x 2 grid."""
     rng = np.random.default_rng(11)
     M, N, K = 1280, 512, 384   # 6 k-tiles: the loop runs (DMA, L2 prefetch past K)
     X = bf16(rng.standard_normal((M, K)))
@@ -82,19 +82,16 @@ def test_asm_gemm_variants_match_product_kernel(variant):
     close(tof(out[0]), tof(X) @ tof(W).T)
 
 
-PERSIST_ARMS = [v for v, k in gemm_gen.PLAIN_VARIANTS if k.get("persist") and k.get("store_nt", True)]
+PERSIST_ARMS = ["v3"]
 
 
 @pytest.mark.parametrize("arm", PERSIST_ARMS)
 @pytest.mark.parametrize("grid,K", [(1, 320), (3, 320), (10, 320), (3, 192), (4, 256)])
 def test_asm_gemm_persistent_arm_emulated(arm, grid, K):
-    """The persistent arms: `grid` workgroups walk the 10 tiles of a 5 x 2
-    grid (S_ITER += grid), staging the next tile under the epilogue (v3) or
-    parking the finished tile's C in AGPRs and storing it during the next
-    tile's first k-iteration (v9, deferred stores: the first tile's stores
-    dropped by a zero-size resource, the last tile's stored at once); C
+    """The persistent arm: `grid` workgroups walk the 10 tiles of a 5 x 2
+    grid (S_ITER += grid), staging the next tile under the epilogue; C
     equals the product kernel's bit for bit.  K = 320: odd k-tile count (the
-    stage parity fix-up); 192: v9's peeled first iteration and no loop."""
+    stage parity fix-up); 192: three k-tiles, one pass of the loop."""
     name = f"toa_gemm_tn_asm_plain_{arm}"
     rng = np.random.default_rng(13)
     M, N = 1280, 512
@@ -314,7 +311,7 @@ def test_asm_gemm_tile_maps_emulated(tile_map):
 def test_asm_gemm_persistent_refuses_zero_grid():
     """A persistent arm given grid 0 (it would walk its first tile forever)
     ends before any memory access."""
-    name = next(f"toa_gemm_tn_asm_plain_{v}" for v, k in gemm_gen.PLAIN_VARIANTS if k.get("persist"))
+    name = "toa_gemm_tn_asm_plain_v3"
     M, N, K = 256, 256, 128
     mem = emu.Memory()
     ax, aw = mem.add(np.ones((M, K), np.uint16)), mem.add(np.ones((N, K), np.uint16))
@@ -337,26 +334,29 @@ def test_asm_gemm_rejects_bad_tile_map():
 
 
 def test_host_kernel_table_matches_generator():
-    """Every kernel name csrc/hip/gemm_asm.hip resolves exists in the code
-    object (a missing one fails the module load, i.e. every asm GEMM)."""
+    """csrc/hip/gemm_asm.hip's one kernel table against the code object: the
+    names it resolves (a missing one fails the module load, i.e. every asm
+    GEMM) are exactly the kernels the generators emit, NN form included, one
+    per member of the enum, as many as the generators' tables say."""
     import re
 
-    src = open(os.path.join(os.path.dirname(HERE), "csrc", "hip", "gemm_asm.hip")).read()
-    generated = set(re.findall(r"^(toa_\w+):", TEXT, re.M))
-    wanted = re.findall(r'"(toa_(?:gemm_tn_asm|wgrad_nt_asm|attn_fwd_asm|attn_dkdv_asm)\w*)"', src)
-    assert wanted and set(wanted) <= generated, set(wanted) - generated
-    n = int(re.search(r"K_N = (\d+)", src).group(1))
-    # + the weight gradient's round-4 arm + the attention forward and its arms + the dK/dV backward
     import attn_bwd_gen
     import attn_gen
-    # + the round-4 SwiGLU epilogue arms (2) + the SwiGLU backward's diagnostic arms
-    # 11: the six product epilogues (plain, swiglu_fwd, swiglu_bwd, rope, delta, resadd), probe, trace, timing,
-    # timing2, wgrad
-    assert n == len(wanted) == 11 + len(gemm_gen.PLAIN_VARIANTS) + 2 + len(attn_gen.VARIANTS) + 1 + \
-        len(attn_bwd_gen.VARIANTS) + 2 + len(gemm_gen.SWIGLU_BWD_VARIANTS) + len(gemm_gen.SWIGLU_PERSIST_VARIANTS)
-    flags = re.search(r"kVariantPersist\[kNumPlainVariants\] = \{([^}]*)\}", src).group(1)
-    assert int(re.search(r"kNumPlainVariants = (\d+)", src).group(1)) == len(gemm_gen.PLAIN_VARIANTS)
-    assert [f.strip() == "true" for f in flags.split(",")] == [bool(k.get("persist")) for _, k in gemm_gen.PLAIN_VARIANTS]
+
+    src = open(os.path.join(os.path.dirname(HERE), "csrc", "hip", "gemm_asm.hip")).read()
+    generated = re.findall(r"^    \.name: (toa_\w+)$", TEXT, re.M)          # the code object's metadata
+    assert len(set(generated)) == len(generated)
+    assert set(generated) == set(re.findall(r"^(toa_\w+):", TEXT, re.M))
+    names = re.findall(r'"(toa_\w+)"', re.search(r"kNames\[\] = \{(.*?)\};", src, re.S).group(1))
+    assert len(set(names)) == len(names) and set(names) == set(generated), set(names) ^ set(generated)
+    enum = [m.strip() for m in re.sub(r"//[^\n]*", "", re.search(r"enum \{(\s*K_PLAIN,.*?)\};", src, re.S).group(1)).split(",")]
+    assert enum[-1] == "K_N" and len(enum) - 1 == len(names)          # K_N, the last member, is the array's length
+    assert "static_assert(sizeof(kNames) / sizeof(kNames[0]) == K_N" in src
+    # the epilogues of both forms, their persistent arms, the weight gradient, probe + trace + the timing
+    # kernels, the attention forward and the dK/dV backward each with their variants
+    assert len(names) == len(gemm_gen.EPIS) + len(gemm_gen.NN_EPIS) + len(gemm_gen.PLAIN_VARIANTS) + \
+        len(gemm_gen.SWIGLU_PERSIST_VARIANTS) + 1 + 2 + len(gemm_gen.TIMING_VARIANTS) + \
+        1 + len(attn_gen.VARIANTS) + 1 + len(attn_bwd_gen.VARIANTS)
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/clang"), reason="no ROCm LLVM")

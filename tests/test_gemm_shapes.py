@@ -33,3 +33,14 @@ def test_python_form_names_follow_the_header():
     assert names[-1] == "COUNT"
     assert tuple(n.lower() for n in names[:-1]) == _lib.SHAPE_FORMS
     assert len(_lib._SIGS["toa_gemm_shape_check"]) == 18
+
+
+def test_every_ctypes_signature_names_an_export():
+    """Every launcher ops/_lib.py declares argument types for is exported by
+    libtoa_hip.so: _load skips a missing one silently, so a row left behind
+    when an entry point is deleted would otherwise go unnoticed."""
+    from tf_operator_amd.ops import _lib
+
+    assert _lib.available(), _lib.load_error()
+    missing = sorted(n for n in list(_lib._SIGS) + sorted(_lib._TYPED_ELSEWHERE) if not hasattr(_lib.lib(), n))
+    assert not missing, missing

@@ -101,7 +101,6 @@ _SIGS = {
     "toa_accuracy": [c_int, c_p, c_p, c_p, c_int, c_int, c_p],
     "toa_attn_fwd": [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p],
     "toa_attn_fwd_asm": [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p],
-    "toa_attn_fwd_asm_variant": [c_int, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p],
     "toa_attn_fwd_asm_timing": [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f,
                                 c_p],
     "toa_attn_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -117,8 +116,6 @@ _SIGS = {
     "toa_wgrad": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],
     "toa_wgrad_split": [c_int, c_int, c_int],
     "toa_wgrad_asm": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],
-    "toa_wgrad_asm_variant": [c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int,
-                              c_p],
     "toa_wgrad_reduce": [c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p],
     "toa_transpose_bf16": [c_p, c_i64, c_p, c_i64, c_int, c_int, c_p],
     "toa_gemm": [c_int, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_f, c_int, c_p],
@@ -135,19 +132,15 @@ _SIGS = {
     "toa_gemm_asm_rows": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_swiglu_bwd": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
-    "toa_gemm_asm_swiglu_bwd_variant": [c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_available": [],
     "toa_gemm_asm_trace": [c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_host_free": [c_p],
     "toa_gemm_asm_stage": [c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
-    "toa_gemm_asm_variant": [c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_map": [c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
-    "toa_gemm_asm_set_epi_variant": [c_int],
     "toa_gemm_asm_set_phase": [c_int, ctypes.c_uint],
     "toa_wgrad_asm_set_map": [c_int],
     "toa_gemm_asm_set_map": [c_int],
     "toa_gemm_asm_set_persist": [c_int],
-    "toa_attn_dkdv_asm_set_arm": [c_int],
     "toa_gemm_asm_timing": [c_int, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_gemm_asm_probe": [c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p],
     "toa_attn_set_bwd_variant": [c_int],
@@ -157,8 +150,6 @@ _SIGS = {
     "toa_attn_set_dkdv_variant": [c_int],
     "toa_attn_dkdv_asm": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_f, c_int,
                           c_p, c_p, c_int, c_p],
-    "toa_attn_dkdv_asm_variant": [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
-                                  c_f, c_int, c_p, c_p, c_int, c_p],
     "toa_attn_dkdv_asm_timing": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
                                  c_f, c_int, c_p, c_p, c_int, c_p],
     "toa_attn_bwd_rope": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int,

@@ -486,10 +486,9 @@ def wgrad_kernel() -> str:
 
 
 def set_wgrad_kernel(name: str):
-    """asm | hip | asm_v1 (the round-4 assembly schedule, bit-identical: the
-    round-to-round A/B of scripts/wgrad_inmodel_ab.py)."""
+    """asm | hip (the in-process A/B of scripts/wgrad_inmodel_ab.py)."""
     global _WGRAD_KERNEL
-    if name not in ("asm", "hip", "asm_v1"):
+    if name not in ("asm", "hip"):
         raise ValueError(f"unknown weight-gradient kernel {name!r}")
     _WGRAD_KERNEL = name
 
@@ -516,7 +515,7 @@ def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:
 
 
 def _wgrad_asm_selected() -> bool:
-    return wgrad_kernel() in ("asm", "asm_v1") and _lib.has("toa_wgrad_asm_workspace")
+    return wgrad_kernel() == "asm" and _lib.has("toa_wgrad_asm_workspace")
 
 
 def _wgrad_gate_why(g, dy2, x2) -> str:
@@ -657,15 +656,14 @@ def wgrad_hip_(g, dy2, x2, beta=1.0, split=None):
     args = (_lib.ptr(dy2), dy2.stride(0), _lib.ptr(x2), x2.stride(0), _lib.ptr(g), K, _lib.ptr(ws),
             N, K, T, int(split), int(beta != 0.0), _lib.stream(dy2))
     kern = wgrad_kernel()
-    if kern in ("asm", "asm_v1"):
+    if kern == "asm":
         # the gradient-norm partials stay on the token counts they were
         # measured at (both kernels' common ones); elsewhere the optimizer's
         # full pass over the gradient gives the clipping norm
         sess = _session_for(g) if _SESSIONS and hip_takes else None
         armed = sess is not None and sess.arm(g)
         try:
-            rc = (_lib.call_ret("toa_wgrad_asm", *args) if kern == "asm"
-                  else _lib.call_ret("toa_wgrad_asm_variant", 1, *args))
+            rc = _lib.call_ret("toa_wgrad_asm", *args)
         finally:
             if armed:
                 _lib.call("toa_wgrad_asm_set_sumsq", None)   # one-shot: never left for another launch
@@ -680,7 +678,7 @@ def wgrad_hip_(g, dy2, x2, beta=1.0, split=None):
     if not hip_takes:
         raise RuntimeError(f"weight gradient {N}x{K}x{T}: csrc/hip/wgrad.hip does not take it ("
                            + _lib.shape_why(_wgrad_reason("wgrad_hip", g, dy2, x2, split)) + ") and the assembly kernel "
-                           + ("refused the operands" if kern in ("asm", "asm_v1") else f"is not selected ({kern})"))
+                           + ("refused the operands" if kern == "asm" else f"is not selected ({kern})"))
     _lib.call("toa_wgrad", *args)
     return g
 

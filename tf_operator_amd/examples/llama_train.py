@@ -57,6 +57,9 @@ def main(argv=None):
                         "decoding) and prints one JSON line {\"sample\": {\"step\", \"tokens\"}}; 0 = never")
     p.add_argument("--sample-tokens", type=int, default=16, metavar="M", help="new tokens per sample")
     p.add_argument("--sample-prompt-len", type=int, default=8, metavar="P", help="prompt tokens per sample")
+    p.add_argument("--sample-gemm", choices=["tile", "skinny"], default=None,
+                   help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
+                        "weight-streaming GEMM for 1 to 16 rows (skinny); default: TOA_DECODE_GEMM, else tile")
     a = p.parse_args(argv)
     if a.sample_every < 0 or a.sample_tokens < 1 or a.sample_prompt_len < 1:
         p.error("--sample-every needs N >= 0, --sample-tokens and --sample-prompt-len at least 1")
@@ -99,7 +102,7 @@ def _sample(a, tr, tokens):
     was (LlamaTrainer.generate); the token list's copy to the host is the
     only synchronisation."""
     P = a.sample_prompt_len
-    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens)
+    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm)
     print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
 
 

@@ -24,7 +24,8 @@ import math
 
 import torch
 
-from ..ops.decode import KVCache, attn_decode, check_split_keys, rope_append
+from ..ops.decode import KVCache, attn_decode, check_gemm, check_split_keys, rope_append
+from ..ops import decode as _dec
 from ..ops.embedding import Embedding
 from ..ops.linear import linear
 from ..ops.llm import (attention_block, causal_attention, cross_entropy, rope_cossin, rope_qkv, rope_tables, swiglu_mlp,
@@ -201,24 +202,28 @@ class Llama(torch.nn.Module):
         if cache.batch != B:
             raise ValueError(f"KV cache of {cache.batch} rows for a batch of {B}")
 
-    def _logits_of(self, h, delta, rows=None):
-        """Final norm and head of the residual stream h (+ delta); rows: an index into the tokens."""
+    def _logits_of(self, h, delta, rows=None, gemm="tile"):
+        """Final norm and head of the residual stream h (+ delta); rows: an index into the tokens;
+        gemm: what runs the head GEMM (ops.decode.project)."""
         _, x = self.norm(h, delta)
         if rows is not None:
             x = x[rows]
         head = self.head_weight()
         reading(head, "lm_head")
-        return linear(x, head)
+        return _dec.project(x, head, gemm)
 
     @torch.no_grad()
-    def prefill(self, tokens, cache, lengths=None):
+    def prefill(self, tokens, cache, lengths=None, gemm=None):
         """Run the prompts tokens [B, P] (ragged ones right-padded; lengths:
         host ints, default P each) through the training ops, copy every
         layer's rotated K and V into the cache and return the logits [B, V] of
         position lengths[b]-1.  Causality keeps the pads out of every valid
-        position, and cache slots at or beyond lengths[b] are never read."""
+        position, and cache slots at or beyond lengths[b] are never read.
+        gemm: as in decode_step; here only the head GEMM on the B last
+        positions' rows changes."""
         cfg = self.cfg
         B, P = tokens.shape
+        gemm = check_gemm(gemm)
         self._check_cache(cache, B)
         lengths = [P] * B if lengths is None else [int(n) for n in lengths]
         if len(lengths) != B or min(lengths) < 1 or max(lengths) > P:
@@ -243,16 +248,24 @@ class Llama(torch.nn.Module):
             delta = swiglu_mlp(x, blk.wgu, blk.wd)
         cache.set_lengths(lengths)
         last = torch.tensor([b * P + n - 1 for b, n in enumerate(lengths)], device=tokens.device)
-        return self._logits_of(h, delta, last)
+        return self._logits_of(h, delta, last, gemm)
 
     @torch.no_grad()
-    def decode_step(self, tokens, cache, split_keys=None):
+    def decode_step(self, tokens, cache, split_keys=None, gemm=None):
         """One new token per row, tokens [B], against the cache: appends the
         token's rotated K and V at each row's length and returns the logits
         [B, V] of that position.  No host synchronisation; past the cache's
-        capacity it raises ValueError before any launch."""
+        capacity it raises ValueError before any launch.
+
+        gemm: what runs the seven projections per layer and the head.
+        ``tile``: the training GEMMs (ops.linear.linear, swiglu_mlp);
+        ``skinny``: the weight-streaming GEMM for 1 to 16 rows (ops.gemm
+        linear_skinny / swiglu_skinny), the tile path for operands it
+        refuses; None: TOA_DECODE_GEMM, default ``tile``.  Anything else
+        raises ValueError before a launch."""
         cfg = self.cfg
         (B,) = tokens.shape
+        gemm = check_gemm(gemm)
         self._check_cache(cache, B)
         split_keys = check_split_keys(split_keys)
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
@@ -266,8 +279,8 @@ class Llama(torch.nn.Module):
                 x = blk.attn_norm(h)
             else:
                 h, x = blk.attn_norm(h, delta)
-            q = rope_append(linear(x, blk.wqkv), cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D)
+            q = rope_append(_dec.project(x, blk.wqkv, gemm), cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D)
             o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len)
-            h, x = blk.mlp_norm(h, linear(o.view(B, Hq * D), blk.wo))
-            delta = swiglu_mlp(x, blk.wgu, blk.wd)
-        return self._logits_of(h, delta)
+            h, x = blk.mlp_norm(h, _dec.project(o.view(B, Hq * D), blk.wo, gemm))
+            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm)
+        return self._logits_of(h, delta, gemm=gemm)

@@ -167,6 +167,14 @@ _SIGS = {
     "toa_gemm_kernel_name": [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_p, c_int],
     # form, X W C S D, ldx ldw ldc lds, M N K, S H Hq Hkv split (csrc/hip/gemm_asm_shapes.h Operands)
     "toa_gemm_shape_check": [c_int] + [c_p] * 5 + [c_i64] * 4 + [c_int] * 8,
+    # 1 to 16 rows (csrc/hip/gemm_skinny.hip): x ldx w ldw y ldy, M N K, workspace, stream (SwiGLU: s lds, M F K);
+    # the check: form, x w y workspace, ldx ldw ldy, rows behind w, M N K (csrc/hip/gemm_skinny_shapes.h Operands)
+    "toa_gemm_skinny": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_skinny_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_skinny_check": [c_int] + [c_p] * 4 + [c_i64] * 4 + [c_int] * 3,
+    "toa_gemm_skinny_split": [c_int, c_int],
+    "toa_gemm_skinny_slice_steps": [c_int, c_int],
+    "toa_gemm_skinny_set_nt": [c_int],
 }
 
 
@@ -207,6 +215,13 @@ def _load():
         sw = getattr(lib, "toa_gemm_shape_why", None)
         if sw is not None:
             sw.argtypes, sw.restype = [c_int], ctypes.c_char_p
+        for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes"):
+            kw = getattr(lib, name, None)
+            if kw is not None:
+                kw.argtypes, kw.restype = [c_int, c_int], c_i64
+        kw = getattr(lib, "toa_gemm_skinny_why", None)
+        if kw is not None:
+            kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
         _lib = lib
 
 
@@ -233,7 +248,8 @@ def has(name: str) -> bool:
 
 # launchers whose argument / result types _load sets outside _SIGS
 _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coherent_alloc", "toa_wgrad_workspace",
-                    "toa_wgrad_asm_workspace", "toa_gemm_shape_why"}
+                    "toa_wgrad_asm_workspace", "toa_gemm_shape_why", "toa_gemm_skinny_ws_bytes",
+                    "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why"}
 
 
 def _fn(name: str):

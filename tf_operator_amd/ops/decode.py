@@ -13,15 +13,65 @@ never read into a result.
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
 from . import _lib
+from . import gemm as _gemm
+from .linear import linear
+from .llm import swiglu_mlp
 
 HEAD_DIMS = (64, 128)     # the kernels' head-dim instantiations (csrc/hip/decode.hip)
 # keys per workgroup of toa_attn_decode.  Chosen for long caches: 4096 keys x 8 KV heads x 8 rows are 1024
 # workgroups (4 per CU) of 128 KB of K + V each at head_dim 128
 SPLIT_KEYS_DEFAULT = 256
+
+
+GEMMS = ("tile", "skinny")   # what runs a decode step's projections (docs/kernels.md "Decoding")
+# Under ``skinny``, a projection whose training GEMM already has a 256 x 256 tile per CU or more stays on it: at the
+# Llama-3-8B head (128256 x 4096, 501 tiles) the tile kernel measured 6 to 48 % faster than the skinny one at 1, 8 and
+# 16 rows on the same box; at the forms of 16 to 112 tiles it is 1.3 to 7.9 x slower (docs/kernels.md "Decoding").
+TILE_KEEPS_FROM = 256 * 256   # rows of W
+
+
+def check_gemm(gemm) -> str:
+    """gemm (None: TOA_DECODE_GEMM, default ``tile``) as one of GEMMS, else ValueError."""
+    g = os.environ.get("TOA_DECODE_GEMM", "tile") if gemm is None else gemm
+    if g not in GEMMS:
+        raise ValueError(f"{'TOA_DECODE_GEMM' if gemm is None else 'gemm'}={g!r}: expected one of {GEMMS}")
+    return g
+
+
+def project(x, w, gemm="tile"):
+    """x [B, K] w [N, K]^T of a decode step.  ``tile``: ops.linear.linear, the
+    training GEMMs.  ``skinny``: ops.gemm.linear_skinny, except from
+    TILE_KEEPS_FROM rows of W on where the assembly GEMM takes the operands
+    (the head of a large vocabulary: the tile kernel measured faster there);
+    operands the skinny check refuses (more than 16 rows, a non-bf16 GPU
+    model) take the tile path and are counted (ops.gemm.fallbacks, warned
+    once per shape)."""
+    if gemm == "skinny":
+        if w.shape[0] >= TILE_KEEPS_FROM and _gemm.asm_takes(x, w):
+            return linear(x, w)   # the measured dispatch, not a fallback
+        why = _gemm.skinny_refusal(x, w)
+        if not why:
+            return _gemm.linear_skinny(x, w)
+        _gemm._fallback("decode", (x.shape[0], w.shape[0], x.shape[1]), "tile", why)
+    return linear(x, w)
+
+
+def mlp(x, wgu, wd, gemm="tile"):
+    """The Llama MLP of a decode step, x [B, H] -> [B, H].  ``skinny``: the
+    SwiGLU in the gate|up GEMM (ops.gemm.swiglu_skinny: one launch, no
+    [B, 2F] round trip), then the down projection; refused operands as in
+    :func:`project`."""
+    if gemm == "skinny":
+        why = _gemm.skinny_refusal(x, wgu, swiglu=True)
+        if not why:
+            return project(_gemm.swiglu_skinny(x, wgu), wd, gemm)
+        _gemm._fallback("decode", (x.shape[0], wgu.shape[0], x.shape[1]), "tile", why)
+    return swiglu_mlp(x, wgu, wd)
 
 
 def check_split_keys(split_keys) -> int:

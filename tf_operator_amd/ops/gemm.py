@@ -505,6 +505,92 @@ def _workspace(dev, nbytes):
     return t
 
 
+# ---- 1 to 16 rows: the weight-streaming GEMM of the decode step (csrc/hip/gemm_skinny.hip).  What it takes is
+# csrc/hip/gemm_skinny_shapes.h's to say (toa_gemm_skinny_check); this module adds only what a launcher cannot see:
+# the tensors' kind.
+def skinny_reason(x2, w, swiglu: bool = False, y=None, ws=None) -> int:
+    """toa_gemm_skinny_check for y [M, N] = x2 [M, K] w [N, K]^T (swiglu: w =
+    gate | up [2F, K], y = s [M, F]): 0 = taken, else the reason
+    :func:`skinny_why` names.  y and ws default to what the launch wrappers
+    allocate themselves (contiguous, aligned): x2 stands in for them."""
+    M, K = x2.shape
+    N = w.shape[0] // 2 if swiglu else w.shape[0]
+    y_ptr, ldy = (x2.data_ptr(), N) if y is None else (y.data_ptr(), y.stride(0))
+    ws_ptr = x2.data_ptr() if ws is None else ws.data_ptr()
+    return _lib.call_ret("toa_gemm_skinny_check", int(swiglu), x2.data_ptr(), w.data_ptr(), y_ptr, ws_ptr,
+                         x2.stride(0), w.stride(0), ldy, w.shape[0], M, N, K)
+
+
+def skinny_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_skinny_why")(reason).decode()
+
+
+def skinny_refusal(x2, w, swiglu: bool = False) -> str:
+    """Why (x2 [M, K], w [N, K]) are no operands of the 1-to-16-row GEMM, ""
+    if they are: matrices with unit column stride and a common K, bf16 on the
+    GPU (CPU tensors of any float dtype take the fp32 reference), and a shape
+    the launcher's check takes, in its own words."""
+    if not _lib.has("toa_gemm_skinny_check"):
+        return "library built without toa_gemm_skinny"
+    for t in (x2, w):
+        if t.dim() != 2:
+            return f"a {t.dim()}-D tensor, not a matrix"
+        if t.stride(1) != 1:
+            return f"column stride {t.stride(1)}, not 1"
+        if t.is_cuda and t.dtype != torch.bfloat16:
+            return f"dtype {t.dtype}, not bf16"
+    if x2.device != w.device or x2.dtype != w.dtype:
+        return f"x ({x2.dtype}, {x2.device}) and w ({w.dtype}, {w.device}) differ"
+    if w.shape[1] != x2.shape[1]:
+        return f"K={x2.shape[1]} columns against {w.shape[1]} in the weight"
+    r = skinny_reason(x2, w, swiglu)
+    if r:
+        return f"{skinny_why(r)}: M={x2.shape[0]} N={w.shape[0] // 2 if swiglu else w.shape[0]} K={x2.shape[1]}"
+    return ""
+
+
+def skinny_takes(x2, w, swiglu: bool = False) -> bool:
+    """bf16 GPU matrices with unit column stride whose shape toa_gemm_skinny_check accepts."""
+    return x2.is_cuda and w.is_cuda and not skinny_refusal(x2, w, swiglu)
+
+
+def _skinny_call(name, ws_name, x2, w, N, swiglu):
+    r = skinny_refusal(x2, w, swiglu)
+    if r:
+        raise ValueError(f"{name}: {r}")
+    M, K = x2.shape
+    if not _lib.use_hip(x2):
+        return None
+    y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
+    nbytes = int(_lib.call_ret(ws_name, N, K))
+    ws = _workspace(x2.device, nbytes) if nbytes > 0 else None
+    _lib.call(name, _lib.ptr(x2), x2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(y), N, M, N, K, _lib.ptr(ws),
+              _lib.stream(x2))
+    return y
+
+
+def linear_skinny(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """y [M, N] = x2 [M, K] w [N, K]^T for M <= 16 on toa_gemm_skinny: fp32
+    accumulation, one rounding.  Operands skinny_refusal names raise
+    ValueError before a launch; CPU tensors take the fp32 reference."""
+    reading(w, "linear_skinny")
+    y = _skinny_call("toa_gemm_skinny", "toa_gemm_skinny_ws_bytes", x2, w, w.shape[0], False)
+    return (x2.float() @ w.float().t()).to(x2.dtype) if y is None else y
+
+
+def swiglu_skinny(x2: torch.Tensor, wgu: torch.Tensor) -> torch.Tensor:
+    """s [M, F] = silu(x2 Wg^T) * (x2 Wu^T), wgu = gate | up [2F, K], for
+    M <= 16 on toa_gemm_skinny_swiglu: the product is taken from the fp32
+    accumulators and rounded once; gu is never stored."""
+    reading(wgu, "swiglu_skinny")
+    F_ = wgu.shape[0] // 2
+    s = _skinny_call("toa_gemm_skinny_swiglu", "toa_gemm_skinny_swiglu_ws_bytes", x2, wgu, F_, True)
+    if s is None:
+        gu = x2.float() @ wgu.float().t()
+        s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
+    return s
+
+
 def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:
     """toa_gemm_shape_check for g [N, K] (+)= dy2 [T, N]^T x2 [T, K] on the
     assembly ("wgrad_asm") or the HIP ("wgrad_hip") kernel.  g stands in for

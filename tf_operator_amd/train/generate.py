@@ -6,6 +6,8 @@ from __future__ import annotations
 
 import torch
 
+from ..ops.decode import check_gemm
+
 
 def _pick(logits, temperature, top_k, gen):
     """The next token of each row [B] from its logits [B, V]."""
@@ -20,7 +22,7 @@ def _pick(logits, temperature, top_k, gen):
 
 @torch.no_grad()
 def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, top_k=0, eos_id=None, seed=0,
-             capacity=None, split_keys=None):
+             capacity=None, split_keys=None, gemm=None):
     """prompts [B, P] token ids (ragged ones right-padded, lengths: host ints,
     default P each) -> (tokens [B, P + max_new_tokens], lengths int64 [B]):
     row b holds its prompt, then its max_new_tokens new tokens from position
@@ -31,7 +33,9 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     RNG states are neither read nor advanced.  A row that has emitted eos_id
     keeps emitting it (a done mask on the device).  Nothing inside the loop
     synchronises with the host.  capacity: the KV cache's (default: P +
-    max_new_tokens); too small a one raises ValueError before any launch."""
+    max_new_tokens); too small a one raises ValueError before any launch.
+    gemm: what runs the projections of the decode steps and the prefill's head
+    (Llama.decode_step; None: TOA_DECODE_GEMM, default ``tile``)."""
     if prompts.dim() != 2 or prompts.shape[1] < 1:
         raise ValueError(f"prompts {tuple(prompts.shape)} is not [B, P >= 1]")
     if max_new_tokens < 1:
@@ -40,6 +44,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
         raise ValueError(f"temperature {temperature} and top_k {top_k} must not be negative")
     B, P = prompts.shape
     dev = prompts.device
+    gemm = check_gemm(gemm)
     lengths = [P] * B if lengths is None else [int(n) for n in lengths]
     if len(lengths) != B or min(lengths) < 1 or max(lengths) > P:
         raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {B}")
@@ -62,7 +67,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     out[:, :P] = torch.where(cols[None, :P] < at[:, None], prompts, out[:, :P])
     rows = torch.arange(B, device=dev)
     done = torch.zeros(B, device=dev, dtype=torch.bool)
-    logits = model.prefill(prompts, cache, lengths)
+    logits = model.prefill(prompts, cache, lengths, gemm=gemm)
     for t in range(max_new_tokens):
         tok = _pick(logits, temperature, top_k, gen).to(prompts.dtype)
         if eos_id is not None:
@@ -70,5 +75,5 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
             done = done | (tok == pad)
         out[rows, at + t] = tok
         if t + 1 < max_new_tokens:
-            logits = model.decode_step(tok, cache, split_keys=split_keys)
+            logits = model.decode_step(tok, cache, split_keys=split_keys, gemm=gemm)
     return out, at + max_new_tokens

@@ -264,7 +264,8 @@ class LlamaTrainer:
 
     def generate(self, prompts, max_new_tokens, **kw):
         """Sample from the current weights (train/generate.py: KV-cache
-        decoding; its keyword arguments).  Waits for the outstanding update
+        decoding; its keyword arguments, ``gemm="skinny"`` among them: the
+        weight-streaming GEMM for the decode steps).  Waits for the outstanding update
         and every ZeRO-1 gather first, then runs under no_grad in eval mode.
         The trainer's RNG states, gradients, optimizer state and step counter
         are untouched (sampling draws from a generator of its own), so a run

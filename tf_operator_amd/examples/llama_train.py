@@ -60,9 +60,14 @@ def main(argv=None):
     p.add_argument("--sample-gemm", choices=["tile", "skinny"], default=None,
                    help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
                         "weight-streaming GEMM for 1 to 16 rows (skinny); default: TOA_DECODE_GEMM, else tile")
+    p.add_argument("--sample-prefill-chunk", type=int, default=None, metavar="N",
+                   help="prefill a sample's prompt N tokens at a time through the cache-extend kernels instead of all "
+                        "at once through the training ops; default: all at once")
     a = p.parse_args(argv)
     if a.sample_every < 0 or a.sample_tokens < 1 or a.sample_prompt_len < 1:
         p.error("--sample-every needs N >= 0, --sample-tokens and --sample-prompt-len at least 1")
+    if a.sample_prefill_chunk is not None and a.sample_prefill_chunk < 1:
+        p.error("--sample-prefill-chunk needs N >= 1")
     if a.sample_every and a.sample_prompt_len > a.seq_len:
         p.error("--sample-prompt-len is longer than --seq-len")
     a.doc_len = None
@@ -102,7 +107,7 @@ def _sample(a, tr, tokens):
     was (LlamaTrainer.generate); the token list's copy to the host is the
     only synchronisation."""
     P = a.sample_prompt_len
-    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm)
+    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm, prefill_chunk=a.sample_prefill_chunk)
     print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
 
 

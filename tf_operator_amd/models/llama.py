@@ -213,14 +213,20 @@ class Llama(torch.nn.Module):
         return _dec.project(x, head, gemm)
 
     @torch.no_grad()
-    def prefill(self, tokens, cache, lengths=None, gemm=None):
+    def prefill(self, tokens, cache, lengths=None, gemm=None, chunk=None):
         """Run the prompts tokens [B, P] (ragged ones right-padded; lengths:
         host ints, default P each) through the training ops, copy every
         layer's rotated K and V into the cache and return the logits [B, V] of
         position lengths[b]-1.  Causality keeps the pads out of every valid
         position, and cache slots at or beyond lengths[b] are never read.
         gemm: as in decode_step; here only the head GEMM on the B last
-        positions' rows changes."""
+        positions' rows changes.
+
+        chunk=n >= 1: the prompts go through :meth:`extend` n tokens at a
+        time instead (every projection by `gemm`), so the intermediates are
+        those of B n rows, not B P; no pad is written into the cache (slots
+        at or beyond lengths[b] stay as they were) and chunks in which no row
+        has a token left are skipped."""
         cfg = self.cfg
         B, P = tokens.shape
         gemm = check_gemm(gemm)
@@ -230,6 +236,20 @@ class Llama(torch.nn.Module):
             raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {B}")
         if P > cache.capacity:
             raise ValueError(f"KV cache overflow: a prompt of {P} tokens exceeds the capacity {cache.capacity}")
+        if chunk is not None:
+            if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+                raise ValueError(f"chunk must be an int >= 1, not {chunk!r}")
+            cache.set_lengths([0] * B)
+            logits = None
+            for c0 in range(0, max(lengths), chunk):
+                counts = [min(max(n - c0, 0), chunk) for n in lengths]
+                lg = self.extend(tokens[:, c0:c0 + chunk], cache, counts, gemm=gemm)
+                if logits is None:
+                    logits = lg
+                else:   # a row's logits come from the chunk that holds its last token
+                    here = torch.tensor([n > 0 for n in counts], device=lg.device)
+                    logits = torch.where(here[:, None], lg, logits)
+            return logits
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
         cos, sin, _ = self.rope(cache.capacity, tokens.device)
         cos, sin = cos[:P], sin[:P]
@@ -249,6 +269,58 @@ class Llama(torch.nn.Module):
         cache.set_lengths(lengths)
         last = torch.tensor([b * P + n - 1 for b, n in enumerate(lengths)], device=tokens.device)
         return self._logits_of(h, delta, last, gemm)
+
+    @torch.no_grad()
+    def extend(self, tokens, cache, counts=None, split_keys=None, gemm=None, logits="last"):
+        """Append counts[b] (host ints >= 0, not all zero; default T each) of
+        the tokens [B, T] to row b of the cache at its current length: T = 1
+        on a filled cache is a decode step, T = P on an empty one a prefill,
+        anything between a chunk of a prompt, a second turn, or drafted tokens
+        to verify.  Embedding, norms and projections run on the B T rows
+        (ops.decode.project / mlp by `gemm`, as in decode_step: the skinny
+        GEMM applies by its own check when B T <= 16, refused operands take
+        ``tile`` and are counted), RoPE + append and the attention are
+        ops.decode.rope_append_many / attn_extend (split_keys: None is
+        ops.decode.extend_split's choice).
+
+        logits="last": [B, V] at each row's last new token; only those B rows
+        go through the final norm and the head.  "all": [B, T, V].  The
+        logits of a row with count 0, and under "all" those of positions
+        t >= counts[b], are finite but meaningless.  No host synchronisation;
+        past the cache's capacity it raises ValueError before any launch."""
+        cfg = self.cfg
+        if tokens.dim() != 2 or tokens.shape[1] < 1:
+            raise ValueError(f"tokens {tuple(tokens.shape)} is not [B, T >= 1]")
+        B, T = tokens.shape
+        gemm = check_gemm(gemm)
+        self._check_cache(cache, B)
+        if logits not in ("last", "all"):
+            raise ValueError(f"logits={logits!r}: expected 'last' or 'all'")
+        if split_keys is not None:
+            _dec.check_extend_split(split_keys)
+        counts = [T] * B if counts is None else [int(n) for n in counts]
+        if len(counts) != B or max(counts) > T:
+            raise ValueError(f"counts {counts} for tokens {tuple(tokens.shape)}: one per row, at most {T}")
+        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        start, count = cache.extend(counts)
+        max_len = cache.max_len
+        cos, sin, _ = self.rope(cache.capacity, tokens.device)
+        h = self.embed(tokens).view(B * T, cfg.hidden)
+        delta = None
+        for i, blk in enumerate(self.blocks):
+            if delta is None:
+                x = blk.attn_norm(h)
+            else:
+                h, x = blk.attn_norm(h, delta)
+            qkv = _dec.project(x, blk.wqkv, gemm).view(B, T, -1)
+            q = _dec.rope_append_many(qkv, cos, sin, start, count, cache.k[i], cache.v[i], Hq, Hkv, D)
+            o = _dec.attn_extend(q, cache.k[i], cache.v[i], start, count, split_keys=split_keys, max_len=max_len)
+            h, x = blk.mlp_norm(h, _dec.project(o.view(B * T, Hq * D), blk.wo, gemm))
+            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm)
+        if logits == "all":
+            return self._logits_of(h, delta, gemm=gemm).view(B, T, -1)
+        last = torch.tensor([b * T + max(n, 1) - 1 for b, n in enumerate(counts)], device=tokens.device)
+        return self._logits_of(h[last], delta[last], gemm=gemm)
 
     @torch.no_grad()
     def decode_step(self, tokens, cache, split_keys=None, gemm=None):

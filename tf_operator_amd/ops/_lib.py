@@ -113,6 +113,12 @@ _SIGS = {
     # q kcache vcache len workspace o, B Hq Hkv C D max_len split_keys scale
     "toa_decode_rope_append": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p],
     "toa_attn_decode": [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p],
+    # extending the cache (csrc/hip/extend.hip): qkv cos sin start count q kcache vcache, B T Hq Hkv D C table_rows;
+    # q kcache vcache start count workspace o, B T Hq Hkv C D max_len split_keys scale
+    "toa_extend_rope_append": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_p],
+    "toa_attn_extend": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                        c_f, c_p],
     "toa_wgrad": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],
     "toa_wgrad_split": [c_int, c_int, c_int],
     "toa_wgrad_asm": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],

@@ -2,7 +2,9 @@
 one query row per head against the cached keys.
 
 HIP kernels: csrc/hip/decode.hip (``toa_decode_rope_append``,
-``toa_attn_decode``: split over keys, fp32 partials, a merge kernel); CPU
+``toa_attn_decode``: split over keys, fp32 partials, a merge kernel) and, for
+T tokens per row at once (chunked prefill, continuation), csrc/hip/extend.hip
+(``toa_extend_rope_append``, ``toa_attn_extend``: the same split on the MFMA); CPU
 tensors take a plain PyTorch reference (fp32 math, the result in the tensor's
 dtype), row by row, so the CPU tier runs the whole feature.
 
@@ -147,6 +149,27 @@ class KVCache:
         self.host_lengths = [x + n for x in self.host_lengths]
         self._state += n
 
+    def extend(self, counts):
+        """Row b grows by counts[b] slots (host ints >= 0, not all zero).  Past
+        the capacity: ValueError, before any launch and with nothing changed.
+        Advances the host and the device lengths and returns (start, count),
+        int32 [B] on the device, start the lengths before the call.  The device
+        update is queued like set_lengths' copy; nothing waits for the device."""
+        counts = [int(n) for n in counts]
+        if len(counts) != self.batch:
+            raise ValueError(f"{len(counts)} counts for a batch of {self.batch}")
+        if min(counts) < 0 or max(counts) < 1:
+            raise ValueError(f"extend by {counts}: counts must be >= 0 and not all zero")
+        new = [a + n for a, n in zip(self.host_lengths, counts)]
+        if max(new) > self.capacity:
+            raise ValueError(f"KV cache overflow: lengths {self.host_lengths} + {counts} exceed the capacity "
+                             f"{self.capacity}")
+        sc = torch.tensor([self.host_lengths, counts], dtype=torch.int32).to(self.device)
+        n = torch.tensor(new, dtype=torch.int32)
+        self.host_lengths = new
+        self._state.copy_(torch.stack([n - 1, n]))
+        return sc[0], sc[1]
+
 
 def _check_cache(k_cache, v_cache, B, Hkv, D, like):
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
@@ -250,4 +273,137 @@ def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_l
         v = v_cache[b, :, :n].float().repeat_interleave(rep, 0)
         s = torch.matmul(k, q[b].float()[:, :, None]).squeeze(-1) * scale
         out[b] = torch.matmul(torch.softmax(s, -1)[:, None], v).squeeze(1).to(q.dtype)
+    return out
+
+
+# ---- extending the cache by T tokens per row (csrc/hip/extend.hip; docs/kernels.md "Extending the cache")
+EXTEND_QUERY_ROWS = 64    # query rows (token x head of a GQA group) per workgroup of toa_attn_extend
+# Below this many workgroups the keys are split as well (SPLIT_KEYS_DEFAULT), from it on they are not: one
+# workgroup per CU of an MI355X.  A guess: the crossover was not measured (docs/kernels.md "Extending the cache").
+EXTEND_FILLS_FROM = 256
+
+
+def check_extend_split(split_keys) -> int:
+    """split_keys as toa_attn_extend takes it: 0 (one split over all keys) or a power of two >= 64."""
+    s = split_keys
+    if not isinstance(s, int) or isinstance(s, bool) or (s != 0 and (s < 64 or s & (s - 1))):
+        raise ValueError(f"split_keys must be 0 or a power of two >= 64, not {split_keys!r}")
+    return s
+
+
+def extend_split(B, T, Hq, Hkv, max_len) -> int:
+    """The default split_keys of attn_extend: SPLIT_KEYS_DEFAULT while the
+    query tiles x KV heads x rows are fewer than EXTEND_FILLS_FROM workgroups,
+    0 (no split) from there on."""
+    tiles = -(-T * (Hq // Hkv) // EXTEND_QUERY_ROWS)
+    return SPLIT_KEYS_DEFAULT if tiles * Hkv * B < EXTEND_FILLS_FROM else 0
+
+
+def extend_ws_floats(B, T, Hq, D, max_len, split_keys) -> int:
+    """fp32 words of toa_attn_extend's workspace: per (row, token, head, split)
+    D of unnormalised output, the running maximum and the normaliser."""
+    return B * T * Hq * (-(-max_len // split_keys) if split_keys else 1) * (D + 2)
+
+
+def rope_append_many(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D):
+    """T tokens per row: qkv [B, T, (Hq + 2 Hkv) D], cos / sin [rows, D/2]
+    fp32, start and count int32 [B] on the device (KVCache.extend).  Token t
+    of row b sits at position start[b] + t if t < count[b]: q and k are
+    rotated there with rope_append's expressions, k and v stored into that
+    slot of the caches [B, Hkv, C, D]; returns q [B, T, Hq, D].  A token with
+    t >= count[b], or whose position is outside the cache or the table, writes
+    nothing to the caches and a zero q row."""
+    _check_heads(Hq, Hkv, D)
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] != (Hq + 2 * Hkv) * D:
+        raise ValueError(f"qkv {tuple(qkv.shape)} is not [B, T >= 1, (Hq + 2 Hkv) D = {(Hq + 2 * Hkv) * D}]")
+    B, T = qkv.shape[:2]
+    _check_cache(k_cache, v_cache, B, Hkv, D, qkv)
+    start = _check_rows("start", start, B, qkv.device)
+    count = _check_rows("count", count, B, qkv.device)
+    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.dtype != torch.float32:
+        raise ValueError(f"cos / sin {tuple(cos.shape)} {cos.dtype} are not fp32 [rows, D/2 = {D // 2}]")
+    C = k_cache.shape[2]
+    if _lib.use_hip(qkv):
+        if qkv.dtype != torch.bfloat16:
+            raise RuntimeError(f"HIP rope_append_many needs bf16 (got {qkv.dtype})")
+        qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
+        q = torch.empty(B, T, Hq, D, device=qkv.device, dtype=qkv.dtype)
+        _lib.call("toa_extend_rope_append", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(start),
+                  _lib.ptr(count), _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), B, T, Hq, Hkv, D, C,
+                  cos.shape[0], _lib.stream(qkv))
+        return q
+    q = torch.zeros(B, T, Hq, D, dtype=qkv.dtype)
+    x = qkv.view(B, T, Hq + 2 * Hkv, D)
+    d2 = D // 2
+    for b, (s, n) in enumerate(zip(start.tolist(), count.tolist())):
+        n = min(n, T, C - s, cos.shape[0] - s) if s >= 0 else 0
+        if n < 1:
+            continue
+        xb = x[b, :n]
+        x1, x2 = xb[:, :Hq + Hkv, :d2].float(), xb[:, :Hq + Hkv, d2:].float()
+        c, sn = cos[s:s + n, None], sin[s:s + n, None]
+        r = torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn], -1).to(qkv.dtype)     # [n, Hq + Hkv, D]
+        q[b, :n] = r[:, :Hq]
+        k_cache[b, :, s:s + n] = r[:, Hq:].transpose(0, 1)
+        v_cache[b, :, s:s + n] = xb[:, Hq + Hkv:].transpose(0, 1)
+    return q
+
+
+def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, max_len=None, workspace=None):
+    """q [B, T, Hq, D] against the caches [B, Hkv, C, D]: query (b, t, h),
+    t < count[b], attends keys 0 .. start[b] + t of KV head h / (Hq / Hkv) --
+    its own key is in the cache already, rope_append_many ran first; returns
+    O [B, T, Hq, D], rows of zeros for tokens with t >= count[b].
+
+    On the GPU: toa_attn_extend, both products on the MFMA, split_keys keys
+    per workgroup (0: one split; a power of two >= 64; None: extend_split)
+    and a merge kernel.  max_len: a host-side bound of start + count
+    (KVCache.max_len; None: the capacity) that sizes the grid -- nothing is
+    read back from the device.  workspace: fp32, at least extend_ws_floats
+    words (None: torch.empty).  At a fixed split_keys a token's result
+    depends on its q row, its cache row's keys 0 .. position, the position
+    and split_keys only -- not on T, its index in the call, count, max_len or
+    the batch."""
+    if q.dim() != 4 or q.shape[1] < 1:
+        raise ValueError(f"q {tuple(q.shape)} is not [B, T >= 1, Hq, D]")
+    B, T, Hq, D = q.shape
+    if k_cache.dim() != 4:
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} is not [B, Hkv, C, D]")
+    Hkv, C = k_cache.shape[1], k_cache.shape[2]
+    _check_heads(Hq, Hkv, D)
+    _check_cache(k_cache, v_cache, B, Hkv, D, q)
+    start = _check_rows("start", start, B, q.device)
+    count = _check_rows("count", count, B, q.device)
+    max_len = C if max_len is None else int(max_len)
+    if not 1 <= max_len <= C:
+        raise ValueError(f"max_len {max_len} outside 1 .. capacity {C}")
+    split = check_extend_split(extend_split(B, T, Hq, Hkv, max_len) if split_keys is None else split_keys)
+    words = extend_ws_floats(B, T, Hq, D, max_len, split)
+    if workspace is not None:
+        if (workspace.dtype != torch.float32 or workspace.device != q.device or not workspace.is_contiguous()
+                or workspace.numel() < words or workspace.data_ptr() % 16):
+            raise ValueError(f"workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {words} words "
+                             f"on {q.device} (got {workspace.dtype} x {workspace.numel()} on {workspace.device})")
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    if _lib.use_hip(q):
+        if q.dtype != torch.bfloat16:
+            raise RuntimeError(f"HIP attn_extend needs bf16 (got {q.dtype})")
+        q = q.contiguous()
+        ws = torch.empty(words, device=q.device, dtype=torch.float32) if workspace is None else workspace
+        o = torch.empty_like(q)
+        _lib.call("toa_attn_extend", _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(start),
+                  _lib.ptr(count), _lib.ptr(ws), _lib.ptr(o), B, T, Hq, Hkv, C, D, max_len, split, scale,
+                  _lib.stream(q))
+        return o
+    rep = Hq // Hkv
+    out = torch.zeros(B, T, Hq, D, dtype=q.dtype)
+    for b, (s, cnt) in enumerate(zip(start.tolist(), count.tolist())):
+        if s < 0:
+            continue
+        kb = k_cache[b].float().repeat_interleave(rep, 0)     # [Hq, C, D]
+        vb = v_cache[b].float().repeat_interleave(rep, 0)
+        for t in range(min(cnt, T, C - s)):
+            n = min(s + t + 1, max_len)
+            sc = torch.matmul(kb[:, :n], q[b, t].float()[:, :, None]).squeeze(-1) * scale
+            out[b, t] = torch.matmul(torch.softmax(sc, -1)[:, None], vb[:, :n]).squeeze(1).to(q.dtype)
     return out

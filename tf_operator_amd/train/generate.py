@@ -22,7 +22,7 @@ def _pick(logits, temperature, top_k, gen):
 
 @torch.no_grad()
 def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, top_k=0, eos_id=None, seed=0,
-             capacity=None, split_keys=None, gemm=None):
+             capacity=None, split_keys=None, gemm=None, prefill_chunk=None):
     """prompts [B, P] token ids (ragged ones right-padded, lengths: host ints,
     default P each) -> (tokens [B, P + max_new_tokens], lengths int64 [B]):
     row b holds its prompt, then its max_new_tokens new tokens from position
@@ -35,7 +35,10 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     synchronises with the host.  capacity: the KV cache's (default: P +
     max_new_tokens); too small a one raises ValueError before any launch.
     gemm: what runs the projections of the decode steps and the prefill's head
-    (Llama.decode_step; None: TOA_DECODE_GEMM, default ``tile``)."""
+    (Llama.decode_step; None: TOA_DECODE_GEMM, default ``tile``).
+    prefill_chunk: Llama.prefill's chunk (None: the whole prompt at once
+    through the training ops; n >= 1: n tokens at a time through the
+    cache-extend kernels)."""
     if prompts.dim() != 2 or prompts.shape[1] < 1:
         raise ValueError(f"prompts {tuple(prompts.shape)} is not [B, P >= 1]")
     if max_new_tokens < 1:
@@ -67,7 +70,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     out[:, :P] = torch.where(cols[None, :P] < at[:, None], prompts, out[:, :P])
     rows = torch.arange(B, device=dev)
     done = torch.zeros(B, device=dev, dtype=torch.bool)
-    logits = model.prefill(prompts, cache, lengths, gemm=gemm)
+    logits = model.prefill(prompts, cache, lengths, gemm=gemm, chunk=prefill_chunk)
     for t in range(max_new_tokens):
         tok = _pick(logits, temperature, top_k, gen).to(prompts.dtype)
         if eos_id is not None:

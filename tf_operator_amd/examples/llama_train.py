@@ -63,9 +63,29 @@ def main(argv=None):
     p.add_argument("--sample-prefill-chunk", type=int, default=None, metavar="N",
                    help="prefill a sample's prompt N tokens at a time through the cache-extend kernels instead of all "
                         "at once through the training ops; default: all at once")
+    p.add_argument("--sample-temperature", type=float, default=0.0, metavar="T",
+                   help="temperature of a sample; 0 = greedy (the default)")
+    p.add_argument("--sample-top-k", type=int, default=0, metavar="K", help="keep a sample's K likeliest tokens; 0 = all")
+    p.add_argument("--sample-top-p", type=float, default=1.0, metavar="P",
+                   help="nucleus filter of a sample, in (0, 1]; below 1 it needs --sample-sampler device")
+    p.add_argument("--sample-min-p", type=float, default=0.0, metavar="P",
+                   help="drop a sample's tokens below P times the mode's probability, in [0, 1); above 0 it needs "
+                        "--sample-sampler device")
+    p.add_argument("--sample-seed", type=int, default=0, metavar="S", help="seed of a sample's draws, 0 .. 2^32 - 1")
+    p.add_argument("--sample-sampler", choices=["torch", "device"], default=None,
+                   help="what picks a sample's tokens: library calls on one generator (torch) or the sampling kernel "
+                        "(device); default: TOA_SAMPLER, else torch")
     a = p.parse_args(argv)
     if a.sample_every < 0 or a.sample_tokens < 1 or a.sample_prompt_len < 1:
         p.error("--sample-every needs N >= 0, --sample-tokens and --sample-prompt-len at least 1")
+    if not (0.0 <= a.sample_temperature < float("inf")) or a.sample_top_k < 0:
+        p.error("--sample-temperature needs a finite T >= 0, --sample-top-k needs K >= 0")
+    if not 0.0 < a.sample_top_p <= 1.0 or not 0.0 <= a.sample_min_p < 1.0:
+        p.error("--sample-top-p needs 0 < P <= 1, --sample-min-p needs 0 <= P < 1")
+    if not 0 <= a.sample_seed < 1 << 32:
+        p.error("--sample-seed needs 0 <= S < 2^32")
+    if (a.sample_top_p < 1.0 or a.sample_min_p > 0.0) and a.sample_sampler == "torch":
+        p.error("--sample-top-p and --sample-min-p need --sample-sampler device")
     if a.sample_prefill_chunk is not None and a.sample_prefill_chunk < 1:
         p.error("--sample-prefill-chunk needs N >= 1")
     if a.sample_every and a.sample_prompt_len > a.seq_len:
@@ -102,12 +122,14 @@ def _stop_agreed(rt, dev) -> bool:
 
 
 def _sample(a, tr, tokens):
-    """One greedy sample from the first --sample-prompt-len tokens of the
-    batch's first row, as one JSON line on stdout.  It leaves the run as it
-    was (LlamaTrainer.generate); the token list's copy to the host is the
-    only synchronisation."""
+    """One sample (greedy unless --sample-temperature is set) from the first
+    --sample-prompt-len tokens of the batch's first row, as one JSON line on
+    stdout.  It leaves the run as it was (LlamaTrainer.generate); the token
+    list's copy to the host is the only synchronisation."""
     P = a.sample_prompt_len
-    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm, prefill_chunk=a.sample_prefill_chunk)
+    out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm, prefill_chunk=a.sample_prefill_chunk,
+                         temperature=a.sample_temperature, top_k=a.sample_top_k, top_p=a.sample_top_p,
+                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler)
     print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
 
 

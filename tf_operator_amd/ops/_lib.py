@@ -119,6 +119,10 @@ _SIGS = {
                                c_int, c_p],
     "toa_attn_extend": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                         c_f, c_p],
+    # sampling (csrc/hip/sample.hip): dtype logits ld, B V, temperature top_k top_p min_p stream_id position (per
+    # row), seed, tokens, weights (or null), stream
+    "toa_sample_tokens": [c_int, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_uint32, c_p, c_p,
+                          c_p],
     "toa_wgrad": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],
     "toa_wgrad_split": [c_int, c_int, c_int],
     "toa_wgrad_asm": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_p],

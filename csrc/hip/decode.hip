@@ -1,90 +1,38 @@
 // KV-cache decoding for the Llama stack (gfx950): one new token per batch row
 // against a cache of past keys.
 //
-// Cache layout: K and V are [B, Hkv, C, D] bf16 per layer (C = capacity), K
-// stored already rotated, so the keys of one KV head are contiguous -- what a
-// decode step streams.
+// Cache layout (kv_cache.h): K and V are [B, Hkv, C, D] bf16 per layer, the
+// keys of one KV head contiguous -- what a decode step streams.
 //
 //   toa_decode_rope_append  qkv row of the new token -> rotated q [B, Hq, D],
 //                           rotated k and v into slot pos[b] of the caches
+//                           (kv_rope_append_kernel, kv_cache.hip)
 //   toa_attn_decode         q against keys 0 .. len[b]-1, split over keys:
 //                           fp32 partials (max, normaliser, unnormalised O)
-//                           per split into a workspace, then a merge kernel
-//                           writes bf16 [B, Hq, D].  No float atomics; every
-//                           sum runs in a fixed order, so a row's bits depend
-//                           on that row's q, cache, len and split_keys only.
+//                           per split into a workspace, then the merge kernel
+//                           (kv_split_merge_kernel, kv_cache.hip) writes bf16
+//                           [B, Hq, D].  No float atomics; every sum runs in a
+//                           fixed order, so a row's bits depend on that row's
+//                           q, cache, len and split_keys only.
 //
 // The dot products run on the VALU: a decode step reads each K/V byte once for
 // at most 8 query rows (the heads of one GQA group), 1 FMA per byte and head,
 // far below what the vector units issue while HBM delivers the bytes; an MFMA
 // tile would be 8 rows of 16 or 32, idle for the rest, and wants K/V images in
 // LDS that this kernel never needs (docs/kernels.md, "Decoding").
-#include "toa_common.h"
+#include "kv_cache.h"
 
 #include <algorithm>
 
-// ---------------------------------------------------------------------------
-// RoPE at a per-row position + append.  qkv: [B, (Hq + 2 Hkv) D], cos/sin:
-// [tab_rows, D/2] fp32 (ops.llm.rope_tables), pos: [B] int32.  The rotation is
-// rope_fwd_kernel's (llm.hip), expression for expression: the same input row
-// at the same position gives the same q and k bits as the training path.
-// Work unit = one (row, qkv-head, 8-wide pair chunk).  A row whose position is
-// outside the cache or the table writes nothing.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void decode_rope_append_kernel(
-    const bf16_t* __restrict__ qkv, const float* __restrict__ cosv, const float* __restrict__ sinv,
-    const int* __restrict__ pos, bf16_t* __restrict__ q, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int B,
-    int Hq, int Hkv, int D, int C, int tab_rows) {
-  const int half = D / 2, cpd = half / 8;
-  const int H3 = Hq + 2 * Hkv;
-  const int64_t units = (int64_t)B * H3 * cpd;
-  const int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (u >= units) return;
-  const int c = u % cpd;
-  const int64_t r = u / cpd;
-  const int h = r % H3;
-  const int b = r / H3;
-  const int s = pos[b];
-  if (s < 0 || s >= C || s >= tab_rows) return;
-  const bf16_t* src = qkv + b * (int64_t)(H3 * D) + h * D + c * 8;
-  u32x4 x1v = ld16(src), x2v = ld16(src + half);
-  if (h >= Hq + Hkv) {  // V: as it is
-    const int g = h - Hq - Hkv;
-    bf16_t* dst = vc + (((int64_t)b * Hkv + g) * C + s) * D + c * 8;
-    st16(dst, x1v);
-    st16(dst + half, x2v);
-    return;
-  }
-  float x1[8], x2[8], y1[8], y2[8];
-  unpack8(x1v, x1);
-  unpack8(x2v, x2);
-  const float* cp = cosv + (int64_t)s * half + c * 8;
-  const float* sp = sinv + (int64_t)s * half + c * 8;
-  f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
-  f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
-  float cs[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-  float sn[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    y1[j] = x1[j] * cs[j] - x2[j] * sn[j];
-    y2[j] = x2[j] * cs[j] + x1[j] * sn[j];
-  }
-  u32x4 o1 = pack8(y1), o2 = pack8(y2);
-  bf16_t* dst = h < Hq ? q + ((int64_t)b * Hq + h) * D + c * 8
-                       : kc + (((int64_t)b * Hkv + (h - Hq)) * C + s) * D + c * 8;
-  st16(dst, o1);
-  st16(dst + half, o2);
-}
-
+// One token per row at position pos[b]: the shared kernel with T = 1 and no
+// count.  A position outside the cache or the table writes nothing to the
+// caches and a zero q row (KVCache never produces one).
 extern "C" int toa_decode_rope_append(const bf16_t* qkv, const float* cosv, const float* sinv, const int* pos,
                                       bf16_t* q, bf16_t* kc, bf16_t* vc, int B, int Hq, int Hkv, int D, int C,
                                       int tab_rows, hipStream_t stream) {
   if ((D != 64 && D != 128) || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || B <= 0 || C <= 0 || tab_rows <= 0)
     return (int)hipErrorInvalidValue;
-  const int64_t units = (int64_t)B * (Hq + 2 * Hkv) * (D / 16);
-  hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream, qkv,
-                     cosv, sinv, pos, q, kc, vc, B, Hq, Hkv, D, C, tab_rows);
-  return (int)hipGetLastError();
+  return kv_launch_rope_append(qkv, cosv, sinv, pos, nullptr, q, kc, vc, B, 1, Hq, Hkv, D, C, tab_rows, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -101,9 +49,7 @@ extern "C" int toa_decode_rope_append(const bf16_t* qkv, const float* cosv, cons
 // Per iteration a lane has KU K loads and KU V loads of 16 B in flight.
 // At the end the groups' (m, l, acc) merge in a fixed order -- across the
 // groups of a wave by shuffles, across the four waves through LDS -- and the
-// split's partial goes to the workspace:
-//   ws_o  [B, Hq, nsplit, D] fp32 unnormalised output
-//   ws_ml [B, Hq, nsplit, 2] fp32 running max (log2 domain), normaliser
+// split's partial goes to the workspace (kv_cache.h; a row is (b, h)).
 // A split that starts at or beyond len[b] writes nothing; the merge kernel
 // reads the splits below len[b] only.  Keys at or beyond len[b] are never
 // loaded.  A maximum of -inf (no key seen yet) is replaced by 0 before it is
@@ -124,8 +70,6 @@ __device__ __forceinline__ float group_sum(float v) {
   if (LPK == 16) v = dpp_add<0x140>(v);  // row_mirror: the other half of the 16
   return v;
 }
-
-__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // (m, l, acc) <- (m, l, acc) (+) (m2, l2, acc2), the -inf maximum guarded
 __device__ __forceinline__ void part_merge(float& m, float& l, float* acc, float m2, float l2, const float* acc2) {
@@ -280,27 +224,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   }
 }
 
-// One workgroup per (query head, batch row), one thread per column: the
-// row's non-empty splits in order.  len[b] == 0 gives a row of zeros.
-__global__ void attn_decode_merge_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-                                         const int* __restrict__ lens, bf16_t* __restrict__ o, int Hq, int D, int C,
-                                         int split, int nsplit) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  const int len = min(max(lens[b], 0), C);
-  const int ns = min((len + split - 1) / split, nsplit);
-  const int64_t slot0 = ((int64_t)b * Hq + h) * nsplit;
-  float M = -INFINITY;
-  for (int i = 0; i < ns; ++i) M = fmaxf(M, ws_ml[(slot0 + i) * 2]);
-  const float mr = M == -INFINITY ? 0.f : M;
-  float L = 0.f, a = 0.f;
-  for (int i = 0; i < ns; ++i) {
-    const float w = exp2_fast(ws_ml[(slot0 + i) * 2] - mr);
-    L += ws_ml[(slot0 + i) * 2 + 1] * w;
-    a += ws_o[(slot0 + i) * D + d] * w;
-  }
-  o[((int64_t)b * Hq + h) * D + d] = f2bf(L > 0.f ? a / L : 0.f);
-}
-
 template <int D>
 static void launch_decode(int GT, dim3 grid, hipStream_t stream, const bf16_t* q, const bf16_t* kc, const bf16_t* vc,
                           const int* lens, float* ws_o, float* ws_ml, int Hq, int Hkv, int C, int split, int nsplit,
@@ -345,7 +268,5 @@ extern "C" int toa_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* 
     launch_decode<64>(GT, grid, stream, q, kc, vc, lens, ws_o, ws_ml, Hq, Hkv, C, split_keys, nsplit, scale_log2);
   int rc = (int)hipGetLastError();
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(Hq, B), dim3(D), 0, stream, (const float*)ws_o,
-                     (const float*)ws_ml, lens, o, Hq, D, C, split_keys, nsplit);
-  return (int)hipGetLastError();
+  return kv_launch_split_merge(ws_o, ws_ml, lens, nullptr, o, B, 1, Hq, D, C, max_len, split_keys, nsplit, stream);
 }

@@ -3,15 +3,17 @@
 // T = 1 from a filled cache is a decode step, T = P from an empty cache a
 // prefill; everything in between is chunked prefill and continuation.
 //
-// Cache layout as in decode.hip: K and V [B, Hkv, C, D] bf16, K stored rotated.
+// Cache layout (kv_cache.h): K and V [B, Hkv, C, D] bf16, K stored rotated.
 //
 //   toa_extend_rope_append  qkv rows of the T tokens -> rotated q [B, T, Hq, D],
 //                           rotated k and v into slots start[b] + t, t < count[b]
+//                           (kv_rope_append_kernel, kv_cache.hip)
 //   toa_attn_extend         query (b, t, h) against keys 0 .. start[b] + t of its
 //                           KV head (the append ran first: its own key is there),
 //                           split over keys: fp32 partials (max, normaliser,
 //                           unnormalised O) per (row, split) into a workspace,
-//                           then a merge kernel writes bf16 [B, T, Hq, D].
+//                           then the merge kernel (kv_split_merge_kernel,
+//                           kv_cache.hip) writes bf16 [B, T, Hq, D].
 //
 // With T tokens a KV head has T G query rows (G = Hq / Hkv), so both products
 // run on the MFMA (v_mfma_f32_16x16x32_bf16), fp32 scores, softmax and
@@ -31,7 +33,7 @@
 // index in the call, count, max_len or the batch.  Three things carry that:
 // key blocks aligned to absolute key indices, fully masked blocks that are
 // exact no-ops, and a merge over the splits at or below pos, in order.
-#include "toa_common.h"
+#include "kv_cache.h"
 
 typedef __attribute__((ext_vector_type(8))) short ext_s16x8;
 typedef __attribute__((ext_vector_type(4))) short ext_s16x4;
@@ -39,84 +41,11 @@ typedef __attribute__((ext_vector_type(4))) short ext_s16x4;
 #define EXT_KB 64  // keys per block: 4 S^T tiles of 16 keys, 2 k-steps of P V
 #define EXT_QB 64  // query rows per workgroup: one 16-row MFMA tile per wave
 
-__device__ __forceinline__ float ext_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// The last key that token t of a row attends, or -1 for a token that is not
-// there (t >= count, or a position outside the cache).  max_len bounds the keys
-// as it bounds the grid.
-__device__ __forceinline__ int ext_limit(int st, int cnt, int t, int C, int max_len) {
-  if (st < 0 || st >= C || t >= cnt || t >= C - st) return -1;
-  return min(st + t, max_len - 1);
-}
-
 // The largest limit among the query rows r0 .. r1 of a KV head (row r is token
 // r / G): the tokens of a row are there up to the first that is not.
 __device__ __forceinline__ int ext_span_limit(int st, int cnt, int r0, int r1, int G, int C, int max_len) {
-  if (ext_limit(st, cnt, r0 / G, C, max_len) < 0) return -1;
-  return ext_limit(st, cnt, min(min(r1 / G, cnt - 1), C - 1 - st), C, max_len);
-}
-
-// ---------------------------------------------------------------------------
-// RoPE at position start[b] + t, and append.  qkv: [B, T, (Hq + 2 Hkv) D].
-// The rotation is decode_rope_append_kernel's, that is rope_fwd_kernel's
-// (llm.hip), expression for expression.  Work unit = one (row, token, qkv-head,
-// 8-wide pair chunk).  A token with t >= count[b], or whose position is outside
-// the cache or the table, writes nothing to the caches and a zero q row.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void extend_rope_append_kernel(
-    const bf16_t* __restrict__ qkv, const float* __restrict__ cosv, const float* __restrict__ sinv,
-    const int* __restrict__ start, const int* __restrict__ count, bf16_t* __restrict__ q, bf16_t* __restrict__ kc,
-    bf16_t* __restrict__ vc, int B, int T, int Hq, int Hkv, int D, int C, int tab_rows) {
-  const int half = D / 2, cpd = half / 8;
-  const int H3 = Hq + 2 * Hkv;
-  const int64_t units = (int64_t)B * T * H3 * cpd;
-  const int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (u >= units) return;
-  const int c = u % cpd;
-  int64_t r = u / cpd;
-  const int h = r % H3;
-  r /= H3;  // b T + t
-  const int t = r % T;
-  const int b = r / T;
-  const int st = start[b];
-  const bool there = st >= 0 && t < count[b] && st < C && t < C - st && st < tab_rows && t < tab_rows - st;
-  if (!there) {
-    if (h < Hq) {
-      const u32x4 z = {0u, 0u, 0u, 0u};
-      bf16_t* dst = q + (r * Hq + h) * D + c * 8;
-      st16(dst, z);
-      st16(dst + half, z);
-    }
-    return;
-  }
-  const int s = st + t;
-  const bf16_t* src = qkv + r * (int64_t)(H3 * D) + h * D + c * 8;
-  u32x4 x1v = ld16(src), x2v = ld16(src + half);
-  if (h >= Hq + Hkv) {  // V: as it is
-    const int g = h - Hq - Hkv;
-    bf16_t* dst = vc + (((int64_t)b * Hkv + g) * C + s) * D + c * 8;
-    st16(dst, x1v);
-    st16(dst + half, x2v);
-    return;
-  }
-  float x1[8], x2[8], y1[8], y2[8];
-  unpack8(x1v, x1);
-  unpack8(x2v, x2);
-  const float* cp = cosv + (int64_t)s * half + c * 8;
-  const float* sp = sinv + (int64_t)s * half + c * 8;
-  f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
-  f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
-  float cs[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-  float sn[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    y1[j] = x1[j] * cs[j] - x2[j] * sn[j];
-    y2[j] = x2[j] * cs[j] + x1[j] * sn[j];
-  }
-  u32x4 o1 = pack8(y1), o2 = pack8(y2);
-  bf16_t* dst = h < Hq ? q + (r * Hq + h) * D + c * 8 : kc + (((int64_t)b * Hkv + (h - Hq)) * C + s) * D + c * 8;
-  st16(dst, o1);
-  st16(dst + half, o2);
+  if (kv_token_last_key(st, cnt, r0 / G, C, max_len) < 0) return -1;
+  return kv_token_last_key(st, cnt, min(min(r1 / G, cnt - 1), C - 1 - st), C, max_len);
 }
 
 extern "C" int toa_extend_rope_append(const bf16_t* qkv, const float* cosv, const float* sinv, const int* start,
@@ -124,11 +53,7 @@ extern "C" int toa_extend_rope_append(const bf16_t* qkv, const float* cosv, cons
                                       int Hkv, int D, int C, int tab_rows, hipStream_t stream) {
   if ((D != 64 && D != 128) || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || B <= 0 || T < 1 || C <= 0 || tab_rows <= 0)
     return (int)hipErrorInvalidValue;
-  const int64_t blocks = ((int64_t)B * T * (Hq + 2 * Hkv) * (D / 16) + 255) / 256;
-  if (blocks > 0x7fffffff) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(extend_rope_append_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qkv, cosv, sinv, start,
-                     count, q, kc, vc, B, T, Hq, Hkv, D, C, tab_rows);
-  return (int)hipGetLastError();
+  return kv_launch_rope_append(qkv, cosv, sinv, start, count, q, kc, vc, B, T, Hq, Hkv, D, C, tab_rows, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -153,9 +78,7 @@ extern "C" int toa_extend_rope_append(const bf16_t* qkv, const float* cosv, cons
 // (of a 16-key tile) x 16 columns and leaves lane i with column i of those 4
 // keys -- the k order in which the S^T accumulators hold P.
 //
-// Per (row, split) the partial goes to the workspace:
-//   ws_o  [B, T, Hq, nsplit, D] fp32 unnormalised output
-//   ws_ml [B, T, Hq, nsplit, 2] fp32 running max (log2 domain), normaliser
+// Per (row, split) the partial goes to the workspace (kv_cache.h).
 // A row writes its partial of a split only if the split starts at or below the
 // row's limit; the merge kernel reads exactly those.
 // ---------------------------------------------------------------------------
@@ -194,7 +117,7 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restri
   const int wv_lim = __builtin_amdgcn_readfirstlane(ext_span_limit(st, cnt, wv_r0, wv_r0 + 15, G, C, max_len));
   const int myr = wv_r0 + col;
   const int myt = myr / G, myg = myr % G;
-  const int lim = myr < rows ? ext_limit(st, cnt, myt, C, max_len) : -1;
+  const int lim = myr < rows ? kv_token_last_key(st, cnt, myt, C, max_len) : -1;
   const int64_t qrow = ((int64_t)b * T + min(myt, T - 1)) * Hq + kvh * G + myg;
 
   // Q fragments (the B operand): Q[row][32 s + 8 hg .. + 7]
@@ -276,15 +199,15 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restri
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float mn = fmaxf(m, mx);
     const float mr = mn == -INFINITY ? 0.f : mn;
-    const float alpha = mn == m ? 1.f : ext_exp2(m - mr);  // an unchanged maximum rescales by exactly 1
+    const float alpha = mn == m ? 1.f : exp2_fast(m - mr);  // an unchanged maximum rescales by exactly 1
     uint32_t pk[4][2];
     float ps = 0.f;
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int j = 0; j < 4; j += 2) {
-        const float p0 = sc[kt][j] == -INFINITY ? 0.f : ext_exp2(sc[kt][j] - mr);
-        const float p1 = sc[kt][j + 1] == -INFINITY ? 0.f : ext_exp2(sc[kt][j + 1] - mr);
+        const float p0 = sc[kt][j] == -INFINITY ? 0.f : exp2_fast(sc[kt][j] - mr);
+        const float p1 = sc[kt][j + 1] == -INFINITY ? 0.f : exp2_fast(sc[kt][j + 1] - mr);
         const uint32_t w = pack2(p0, p1);  // P is bf16 only as the MFMA operand; the normaliser sums what V sees
         pk[kt][j >> 1] = w;
         ps += __uint_as_float(w << 16);
@@ -325,32 +248,6 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restri
   }
 }
 
-// One workgroup per (batch row, token, query head), one thread per column: the
-// row's splits at or below its position, in order.  A token that is not there
-// gets a row of zeros.
-__global__ void attn_extend_merge_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-                                         const int* __restrict__ start, const int* __restrict__ count,
-                                         bf16_t* __restrict__ o, int T, int Hq, int D, int C, int max_len, int split,
-                                         int nsplit) {
-  const int64_t row = blockIdx.x;  // (b T + t) Hq + h
-  const int d = threadIdx.x;
-  const int64_t bt = row / Hq;
-  const int t = bt % T, b = bt / T;
-  const int lim = ext_limit(start[b], min(count[b], T), t, C, max_len);
-  const int ns = lim < 0 ? 0 : min(lim / split + 1, nsplit);
-  const int64_t slot0 = row * nsplit;
-  float M = -INFINITY;
-  for (int i = 0; i < ns; ++i) M = fmaxf(M, ws_ml[(slot0 + i) * 2]);
-  const float mr = M == -INFINITY ? 0.f : M;
-  float L = 0.f, a = 0.f;
-  for (int i = 0; i < ns; ++i) {
-    const float w = ext_exp2(ws_ml[(slot0 + i) * 2] - mr);
-    L += ws_ml[(slot0 + i) * 2 + 1] * w;
-    a += ws_o[(slot0 + i) * D + d] * w;
-  }
-  o[row * D + d] = f2bf(L > 0.f ? a / L : 0.f);
-}
-
 // q, o [B, T, Hq, D], kc / vc [B, Hkv, C, D] bf16; start, count [B] int32
 // (device); ws: fp32, B T Hq nsplit (D + 2) floats with nsplit =
 // ceil(max_len / split_keys), or 1 for split_keys 0 (one split over all keys).
@@ -383,7 +280,5 @@ extern "C" int toa_attn_extend(const bf16_t* q, const bf16_t* kc, const bf16_t* 
                        Hq, Hkv, C, max_len, split, nsplit, (int)nchunk, scale_log2);
   int rc = (int)hipGetLastError();
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(attn_extend_merge_kernel, dim3((unsigned)mrows), dim3(D), 0, stream, (const float*)ws_o,
-                     (const float*)ws_ml, start, count, o, T, Hq, D, C, max_len, split, nsplit);
-  return (int)hipGetLastError();
+  return kv_launch_split_merge(ws_o, ws_ml, start, count, o, B, T, Hq, D, C, max_len, split, nsplit, stream);
 }

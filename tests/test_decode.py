@@ -7,7 +7,8 @@ The yardstick is ``model(tokens)``, not the code under test.  The teacher-
 forcing and greedy tests run in fp32, the widest dtype the CPU fallbacks
 compute in (they take fp64 tensors too, but do their arithmetic in fp32);
 the tolerance is 3 x the deviation of that fp32 full forward from the same
-model evaluated in fp64 by the plain formulas below (`_forward64`)."""
+model evaluated in fp64 by the plain formulas (decode_numerics.forward64)."""
+import functools
 import json
 import os
 import subprocess
@@ -16,7 +17,7 @@ import sys
 import pytest
 import torch
 
-from tf_operator_amd.models.llama import PRESETS, Llama
+from decode_numerics import fixture, model as _model, row_dev as _row_dev
 from tf_operator_amd.ops import decode as dec
 from tf_operator_amd.ops.llm import rope_tables
 from tf_operator_amd.train.generate import generate
@@ -24,69 +25,9 @@ from tf_operator_amd.train.generate import generate
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROMPT, TOTAL = 5, 45    # prefill 5 tokens, decode the next 40
 # 3 x the fp32 full forward's deviation from fp64, per row relative to the row's norm, is computed from the model
-# at hand (`_fixture`).  Observed on the development machine (llama-tiny, seed 0, 2 x 45 tokens): full forward vs
-# fp64 <= 4.7e-7 of a row's norm, so a tolerance of 1.4e-6; decode vs full forward <= 5.6e-7.
-FACTOR = 3.0
-
-
-def _model(dtype=torch.float32):
-    m = Llama(PRESETS["llama-tiny"], device="cpu", dtype=dtype)
-    m.init_weights(0)
-    return m.eval()
-
-
-def _forward64(model, tokens):
-    """The model's forward in fp64 from the plain formulas: logits [B, S, V]."""
-    cfg = model.cfg
-    B, S = tokens.shape
-    Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-    cos, sin = (t.double() for t in rope_tables(S, D, cfg.rope_theta))   # the model's own (fp32) table values
-
-    def rms(x, w):
-        return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + cfg.norm_eps) * w.double()
-
-    def rope(x):   # [B, H, S, D]
-        x1, x2 = x[..., :D // 2], x[..., D // 2:]
-        return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], -1)
-
-    h = model.embed.weight.double()[tokens]
-    mask = torch.ones(S, S, dtype=torch.bool).triu(1)
-    for blk in model.blocks:
-        x = rms(h, blk.attn_norm.weight)
-        qkv = (x @ blk.wqkv.double().t()).view(B, S, Hq + 2 * Hkv, D).transpose(1, 2)
-        q, k, v = rope(qkv[:, :Hq]), rope(qkv[:, Hq:Hq + Hkv]), qkv[:, Hq + Hkv:]
-        k, v = (t.repeat_interleave(Hq // Hkv, 1) for t in (k, v))
-        s = (q @ k.transpose(-1, -2) / D ** 0.5).masked_fill(mask, float("-inf"))
-        o = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, S, Hq * D)
-        h = h + o @ blk.wo.double().t()
-        x = rms(h, blk.mlp_norm.weight)
-        gu = x @ blk.wgu.double().t()
-        h = h + (torch.nn.functional.silu(gu[..., :cfg.ffn]) * gu[..., cfg.ffn:]) @ blk.wd.double().t()
-    return rms(h, model.norm.weight) @ model.head_weight().double().t()
-
-
-def _row_dev(a, b, ref):
-    """max over rows of ||a - b|| / ||ref||, rows = the last dimension."""
-    return float(((a.double() - b.double()).norm(dim=-1) / ref.double().norm(dim=-1)).max())
-
-
-_CACHE = {}
-
-
-def _fixture():
-    """The fp32 model, a fixed random sequence, its full-forward logits, the
-    fp64 reference and the tolerance that follows; computed once, read-only."""
-    if not _CACHE:
-        m = _model()
-        tokens = torch.randint(0, m.cfg.vocab_size, (2, TOTAL), generator=torch.Generator().manual_seed(5))
-        with torch.no_grad():
-            full = m(tokens)
-            ref = _forward64(m, tokens)
-        dev = _row_dev(full, ref, ref)
-        print(f"fp32 full forward vs fp64: {dev:.3e} of a row's norm -> tolerance {FACTOR * dev:.3e}")
-        assert 0 < dev < 1e-5, dev   # fp32 rounding, nothing else
-        _CACHE.update(model=m, tokens=tokens, full=full, ref=ref, tol=FACTOR * dev)
-    return _CACHE
+# at hand (decode_numerics.fixture).  Observed on the development machine (llama-tiny, seed 0, 2 x 45 tokens): full
+# forward vs fp64 <= 4.7e-7 of a row's norm, so a tolerance of 1.4e-6; decode vs full forward <= 5.6e-7.
+_fixture = functools.partial(fixture, TOTAL)
 
 
 def test_teacher_forcing_matches_the_full_forward():

@@ -6,12 +6,14 @@ positions.
 
 The yardstick is ``model(tokens)``; the fp32 tolerance is the one of
 tests/test_decode.py's teacher-forcing test, 3 x the deviation of the fp32 full
-forward from the same model in fp64 (`_forward64`, the plain formulas), per row
+forward from the same model in fp64 (decode_numerics.forward64), per row
 relative to the row's norm, computed here from the model at hand."""
+import functools
+
 import pytest
 import torch
 
-from tf_operator_amd.models.llama import PRESETS, Llama
+from decode_numerics import fixture, model as _model, row_dev as _row_dev
 from tf_operator_amd.ops import decode as dec
 from tf_operator_amd.ops.llm import rope_tables
 from tf_operator_amd.train.generate import generate
@@ -19,67 +21,7 @@ from tf_operator_amd.train.generate import generate
 TOTAL = 140     # the sequence; chunks of 48 cross 64 and 128
 PROMPT = 70     # prefilled by chunks of 1, 7, 64 (one whole chunk and a tail of 6) and 70, then 10 decode steps
 STEPS = 10
-FACTOR = 3.0
-
-
-def _model(dtype=torch.float32):
-    m = Llama(PRESETS["llama-tiny"], device="cpu", dtype=dtype)
-    m.init_weights(0)
-    return m.eval()
-
-
-def _forward64(model, tokens):
-    """The model's forward in fp64 from the plain formulas: logits [B, S, V]."""
-    cfg = model.cfg
-    B, S = tokens.shape
-    Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-    cos, sin = (t.double() for t in rope_tables(S, D, cfg.rope_theta))
-
-    def rms(x, w):
-        return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + cfg.norm_eps) * w.double()
-
-    def rope(x):   # [B, H, S, D]
-        x1, x2 = x[..., :D // 2], x[..., D // 2:]
-        return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], -1)
-
-    h = model.embed.weight.double()[tokens]
-    mask = torch.ones(S, S, dtype=torch.bool).triu(1)
-    for blk in model.blocks:
-        x = rms(h, blk.attn_norm.weight)
-        qkv = (x @ blk.wqkv.double().t()).view(B, S, Hq + 2 * Hkv, D).transpose(1, 2)
-        q, k, v = rope(qkv[:, :Hq]), rope(qkv[:, Hq:Hq + Hkv]), qkv[:, Hq + Hkv:]
-        k, v = (t.repeat_interleave(Hq // Hkv, 1) for t in (k, v))
-        s = (q @ k.transpose(-1, -2) / D ** 0.5).masked_fill(mask, float("-inf"))
-        o = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, S, Hq * D)
-        h = h + o @ blk.wo.double().t()
-        x = rms(h, blk.mlp_norm.weight)
-        gu = x @ blk.wgu.double().t()
-        h = h + (torch.nn.functional.silu(gu[..., :cfg.ffn]) * gu[..., cfg.ffn:]) @ blk.wd.double().t()
-    return rms(h, model.norm.weight) @ model.head_weight().double().t()
-
-
-def _row_dev(a, b, ref):
-    """max over rows of ||a - b|| / ||ref||, rows = the last dimension."""
-    return float(((a.double() - b.double()).norm(dim=-1) / ref.double().norm(dim=-1)).max())
-
-
-_CACHE = {}
-
-
-def _fixture():
-    """The fp32 model, a fixed random sequence, its full-forward logits, the
-    fp64 reference and the tolerance that follows; computed once, read-only."""
-    if not _CACHE:
-        m = _model()
-        tokens = torch.randint(0, m.cfg.vocab_size, (2, TOTAL), generator=torch.Generator().manual_seed(5))
-        with torch.no_grad():
-            full = m(tokens)
-            ref = _forward64(m, tokens)
-        dev = _row_dev(full, ref, ref)
-        print(f"fp32 full forward vs fp64: {dev:.3e} of a row's norm -> tolerance {FACTOR * dev:.3e}")
-        assert 0 < dev < 1e-5, dev   # fp32 rounding, nothing else
-        _CACHE.update(model=m, tokens=tokens, full=full, ref=ref, tol=FACTOR * dev)
-    return _CACHE
+_fixture = functools.partial(fixture, TOTAL)
 
 
 @pytest.mark.parametrize("chunk", [1, 7, 64, PROMPT])

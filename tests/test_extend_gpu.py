@@ -16,22 +16,16 @@ import pytest
 import torch
 
 import attn_numerics as an
+import decode_numerics as dn
 from attn_numerics import U
+from decode_numerics import DEV, lib as _lib, row_rel as _row_rel
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 NAN = float("nan")
 INVALID_VALUE = 1   # hipErrorInvalidValue
 LAYOUTS = ((2, 2), (4, 1), (4, 2))   # (Hq, Hkv): G = 1, 4, 2
 CAP = 320
-
-
-def _lib():
-    from tf_operator_amd.ops import _lib as L
-
-    assert L.available(), L.load_error()
-    return L
 
 
 def _bits(t):
@@ -228,43 +222,12 @@ def test_launchers_refuse_bad_shapes_and_launch_nothing():
 PROMPT, TOTAL = 70, 140   # chunks of 7 and 64 (a tail of 6), then decode steps across 128
 
 
-@functools.lru_cache(maxsize=None)
 def _teacher(preset):
-    """bf16 model on the GPU, the same weights in fp32 on the CPU (the torch
-    fallbacks), a fixed random sequence [2, TOTAL]; the fp32 reference logits
-    and the bf16 full forward's, [2, TOTAL, V] fp64 on the CPU."""
-    from tf_operator_amd.models.llama import PRESETS, Llama
-
-    m = Llama(PRESETS[preset], device=DEV)
-    m.init_weights(0)
-    m.eval()
-    ref_m = Llama(PRESETS[preset], device="cpu", dtype=torch.float32).eval()
-    ref_m.load_state_dict({k: v.float().cpu() for k, v in m.state_dict().items()})
-    tokens = torch.randint(0, m.cfg.vocab_size, (2, TOTAL), generator=torch.Generator().manual_seed(5))
-    with torch.no_grad():
-        ref = ref_m(tokens).double()
-        full = m(tokens.to(DEV)).double().cpu()
-    return m, ref_m, tokens, ref, full
-
-
-def _row_rel(a, ref):
-    return (a - ref).norm(dim=-1) / ref.norm(dim=-1)
+    return dn.teacher(preset, TOTAL)
 
 
 def _check_teacher(what, got, ref, full, first, D):
-    """got [B, n, V] at positions first .. first + n - 1 within 3 x the full forward's error + the fp32 floor."""
-    n = got.shape[1]
-    ref, full = ref[:, first:first + n], full[:, first:first + n]
-    e_full, e = _row_rel(full, ref), _row_rel(got, ref)
-    limit = 3.0 * e_full + an.fp32_floor(TOTAL, D)
-    ratio = e / limit
-    i = int(ratio.flatten().argmax())
-    b, t = i // n, i % n
-    print(f"{what}: full forward {float(e_full.max()) / U:.3f} u max; {float(e.max()) / U:.3f} u max, "
-          f"{float(e.mean()) / U:.3f} u mean; worst / limit {float(ratio.max()):.3f} at row {b} position {first + t} "
-          f"({float(e[b, t]) / U:.3f} u, full {float(e_full[b, t]) / U:.3f} u)")
-    assert torch.isfinite(got).all()
-    assert bool((e <= limit).all()), (what, b, first + t, float(e[b, t]), float(e_full[b, t]))
+    dn.check_teacher(what, got, ref, full, first, D, TOTAL)
 
 
 @pytest.mark.parametrize("chunk,gemm", [(7, "tile"), (64, "tile"), (7, "skinny")])

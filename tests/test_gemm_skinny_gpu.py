@@ -15,6 +15,7 @@ import torch
 import torch.multiprocessing as mp
 
 import attn_numerics as an
+import decode_numerics as dn
 import skinny_numerics as sn
 import test_decode_gpu as tdg
 
@@ -172,7 +173,7 @@ def test_teacher_forcing_within_three_times_the_full_forwards_error(preset):
     gemm.reset_fallbacks()
     dec = _decode_skinny(m, preset)
     assert not [k for k in gemm.fallbacks() if k.startswith("decode")], gemm.fallbacks()
-    e_full, e_dec, e_tile = tdg._row_rel(full, ref), tdg._row_rel(dec, ref), tdg._row_rel(tile, ref)
+    e_full, e_dec, e_tile = dn.row_rel(full, ref), dn.row_rel(dec, ref), dn.row_rel(tile, ref)
     floor = an.fp32_floor(tdg.TOTAL, m.cfg.head_dim)
     limit = 3.0 * e_full + floor
     ratio = e_dec / limit

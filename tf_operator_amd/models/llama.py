@@ -212,6 +212,23 @@ class Llama(torch.nn.Module):
         reading(head, "lm_head")
         return _dec.project(x, head, gemm)
 
+    def _cached_blocks(self, h, attend, gemm):
+        """The blocks over the rows h [n, hidden] for prefill, extend and
+        decode_step, projections by `gemm` (ops.decode.project / mlp; ``tile``
+        is linear / swiglu_mlp).  attend(layer index, qkv [n, (Hq + 2 Hkv) D])
+        rotates, fills the layer's cache and returns the attention output
+        [n, Hq D].  Returns the residual stream and the last delta."""
+        delta = None
+        for i, blk in enumerate(self.blocks):
+            if delta is None:
+                x = blk.attn_norm(h)
+            else:
+                h, x = blk.attn_norm(h, delta)
+            o = attend(i, _dec.project(x, blk.wqkv, gemm))
+            h, x = blk.mlp_norm(h, _dec.project(o, blk.wo, gemm))
+            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm)
+        return h, delta
+
     @torch.no_grad()
     def prefill(self, tokens, cache, lengths=None, gemm=None, chunk=None):
         """Run the prompts tokens [B, P] (ragged ones right-padded; lengths:
@@ -253,19 +270,14 @@ class Llama(torch.nn.Module):
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
         cos, sin, _ = self.rope(cache.capacity, tokens.device)
         cos, sin = cos[:P], sin[:P]
-        h = self.embed(tokens).view(B * P, cfg.hidden)
-        delta = None
-        for i, blk in enumerate(self.blocks):
-            if delta is None:
-                x = blk.attn_norm(h)
-            else:
-                h, x = blk.attn_norm(h, delta)
-            q, k, v = rope_qkv(linear(x, blk.wqkv), cos, sin, B, P, Hq, Hkv, D, 1)
+
+        def attend(i, qkv):
+            q, k, v = rope_qkv(qkv, cos, sin, B, P, Hq, Hkv, D, 1)
             cache.k[i][:, :, :P] = k
             cache.v[i][:, :, :P] = v
-            o = causal_attention(q, k, v, out_layout="bshd").reshape(B * P, Hq * D)
-            h, x = blk.mlp_norm(h, linear(o, blk.wo))
-            delta = swiglu_mlp(x, blk.wgu, blk.wd)
+            return causal_attention(q, k, v, out_layout="bshd").reshape(B * P, Hq * D)
+
+        h, delta = self._cached_blocks(self.embed(tokens).view(B * P, cfg.hidden), attend, "tile")
         cache.set_lengths(lengths)
         last = torch.tensor([b * P + n - 1 for b, n in enumerate(lengths)], device=tokens.device)
         return self._logits_of(h, delta, last, gemm)
@@ -305,18 +317,13 @@ class Llama(torch.nn.Module):
         start, count = cache.extend(counts)
         max_len = cache.max_len
         cos, sin, _ = self.rope(cache.capacity, tokens.device)
-        h = self.embed(tokens).view(B * T, cfg.hidden)
-        delta = None
-        for i, blk in enumerate(self.blocks):
-            if delta is None:
-                x = blk.attn_norm(h)
-            else:
-                h, x = blk.attn_norm(h, delta)
-            qkv = _dec.project(x, blk.wqkv, gemm).view(B, T, -1)
-            q = _dec.rope_append_many(qkv, cos, sin, start, count, cache.k[i], cache.v[i], Hq, Hkv, D)
+
+        def attend(i, qkv):
+            q = _dec.rope_append_many(qkv.view(B, T, -1), cos, sin, start, count, cache.k[i], cache.v[i], Hq, Hkv, D)
             o = _dec.attn_extend(q, cache.k[i], cache.v[i], start, count, split_keys=split_keys, max_len=max_len)
-            h, x = blk.mlp_norm(h, _dec.project(o.view(B * T, Hq * D), blk.wo, gemm))
-            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm)
+            return o.view(B * T, Hq * D)
+
+        h, delta = self._cached_blocks(self.embed(tokens).view(B * T, cfg.hidden), attend, gemm)
         if logits == "all":
             return self._logits_of(h, delta, gemm=gemm).view(B, T, -1)
         last = torch.tensor([b * T + max(n, 1) - 1 for b, n in enumerate(counts)], device=tokens.device)
@@ -344,15 +351,11 @@ class Llama(torch.nn.Module):
         cos, sin, _ = self.rope(cache.capacity, tokens.device)
         cache.append()
         pos, lens, max_len = cache.positions, cache.lengths, cache.max_len
-        h = self.embed(tokens)
-        delta = None
-        for i, blk in enumerate(self.blocks):
-            if delta is None:
-                x = blk.attn_norm(h)
-            else:
-                h, x = blk.attn_norm(h, delta)
-            q = rope_append(_dec.project(x, blk.wqkv, gemm), cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D)
+
+        def attend(i, qkv):
+            q = rope_append(qkv, cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D)
             o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len)
-            h, x = blk.mlp_norm(h, _dec.project(o.view(B, Hq * D), blk.wo, gemm))
-            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm)
+            return o.view(B, Hq * D)
+
+        h, delta = self._cached_blocks(self.embed(tokens), attend, gemm)
         return self._logits_of(h, delta, gemm=gemm)

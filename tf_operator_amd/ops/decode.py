@@ -4,9 +4,11 @@ one query row per head against the cached keys.
 HIP kernels: csrc/hip/decode.hip (``toa_decode_rope_append``,
 ``toa_attn_decode``: split over keys, fp32 partials, a merge kernel) and, for
 T tokens per row at once (chunked prefill, continuation), csrc/hip/extend.hip
-(``toa_extend_rope_append``, ``toa_attn_extend``: the same split on the MFMA); CPU
-tensors take a plain PyTorch reference (fp32 math, the result in the tensor's
-dtype), row by row, so the CPU tier runs the whole feature.
+(``toa_extend_rope_append``, ``toa_attn_extend``: the same split on the MFMA);
+RoPE + append and the merge are one kernel each for both
+(csrc/hip/kv_cache.hip).  CPU tensors take a plain PyTorch reference (fp32
+math, the result in the tensor's dtype), row by row, so the CPU tier runs the
+whole feature; decoding is its T = 1.
 
 Cache layout: K and V are [B, Hkv, C, D] per layer, C the capacity, K stored
 rotated.  Row b attends slots 0 .. len[b]-1; slots at or beyond len[b] are
@@ -188,41 +190,107 @@ def _check_rows(name, t, B, device):
     return t.contiguous()
 
 
+def _need_bf16(fn, t):
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError(f"HIP {fn} needs bf16 (got {t.dtype})")
+
+
+def _check_rope(qkv, many, cos, sin, rows, k_cache, v_cache, Hq, Hkv, D):
+    """The arguments of rope_append (qkv [B, W]) and, many, of rope_append_many
+    (qkv [B, T, W]); rows: the int32 [B] tensors by name, returned contiguous."""
+    _check_heads(Hq, Hkv, D)
+    width = (Hq + 2 * Hkv) * D
+    if qkv.dim() != 2 + many or (many and qkv.shape[1] < 1) or qkv.shape[-1] != width:
+        raise ValueError(f"qkv {tuple(qkv.shape)} is not [B,{' T >= 1,' if many else ''} (Hq + 2 Hkv) D = {width}]")
+    B = qkv.shape[0]
+    _check_cache(k_cache, v_cache, B, Hkv, D, qkv)
+    rows = [_check_rows(name, t, B, qkv.device) for name, t in rows.items()]
+    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.dtype != torch.float32:
+        raise ValueError(f"cos / sin {tuple(cos.shape)} {cos.dtype} are not fp32 [rows, D/2 = {D // 2}]")
+    return rows
+
+
+def _check_attn(q, many, k_cache, v_cache, rows, max_len, scale):
+    """The arguments of attn_decode (q [B, Hq, D]) and, many, of attn_extend
+    (q [B, T, Hq, D]); rows as in _check_rope.  Returns (rows, max_len, scale)
+    with the defaults filled in."""
+    if q.dim() != 3 + many or (many and q.shape[1] < 1):
+        raise ValueError(f"q {tuple(q.shape)} is not [B,{' T >= 1,' if many else ''} Hq, D]")
+    B, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
+    if k_cache.dim() != 4:
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} is not [B, Hkv, C, D]")
+    Hkv, C = k_cache.shape[1], k_cache.shape[2]
+    _check_heads(Hq, Hkv, D)
+    _check_cache(k_cache, v_cache, B, Hkv, D, q)
+    rows = [_check_rows(name, t, B, q.device) for name, t in rows.items()]
+    max_len = C if max_len is None else int(max_len)
+    if not 1 <= max_len <= C:
+        raise ValueError(f"max_len {max_len} outside 1 .. capacity {C}")
+    return rows, max_len, 1.0 / math.sqrt(D) if scale is None else float(scale)
+
+
+def _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D):
+    """The CPU reference of both rope-appends, qkv [B, T, W]; count None: T
+    each.  A token that is not there (t >= count, a position outside the cache
+    or the table) is skipped: nothing appended, a zero q row."""
+    B, T = qkv.shape[:2]
+    C = k_cache.shape[2]
+    q = torch.zeros(B, T, Hq, D, dtype=qkv.dtype)
+    x = qkv.view(B, T, Hq + 2 * Hkv, D)
+    d2 = D // 2
+    for b, (s, n) in enumerate(zip(start.tolist(), [T] * B if count is None else count.tolist())):
+        n = min(n, T, C - s, cos.shape[0] - s) if s >= 0 else 0
+        if n < 1:
+            continue
+        xb = x[b, :n]
+        x1, x2 = xb[:, :Hq + Hkv, :d2].float(), xb[:, :Hq + Hkv, d2:].float()
+        c, sn = cos[s:s + n, None], sin[s:s + n, None]
+        r = torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn], -1).to(qkv.dtype)     # [n, Hq + Hkv, D]
+        q[b, :n] = r[:, :Hq]
+        k_cache[b, :, s:s + n] = r[:, Hq:].transpose(0, 1)
+        v_cache[b, :, s:s + n] = xb[:, Hq + Hkv:].transpose(0, 1)
+    return q
+
+
+def _attn_ref(q, k_cache, v_cache, start, count, max_len, scale):
+    """The CPU reference of both attentions, q [B, T, Hq, D]: token t < count[b]
+    (None: T each) of row b attends keys 0 .. start[b] + t below max_len;
+    zeros for a token that is not there."""
+    B, T, Hq, D = q.shape
+    C = k_cache.shape[2]
+    rep = Hq // k_cache.shape[1]
+    out = torch.zeros(B, T, Hq, D, dtype=q.dtype)
+    for b, (s, cnt) in enumerate(zip(start.tolist(), [T] * B if count is None else count.tolist())):
+        if s < 0:
+            continue
+        kb = k_cache[b].float().repeat_interleave(rep, 0)     # [Hq, C, D]
+        vb = v_cache[b].float().repeat_interleave(rep, 0)
+        for t in range(min(cnt, T, C - s)):
+            n = min(s + t + 1, max_len)
+            sc = torch.matmul(kb[:, :n], q[b, t].float()[:, :, None]).squeeze(-1) * scale
+            out[b, t] = torch.matmul(torch.softmax(sc, -1)[:, None], vb[:, :n]).squeeze(1).to(q.dtype)
+    return out
+
+
 def rope_append(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv, D):
     """One token per row: qkv [B, (Hq + 2 Hkv) D] (the fused projection's
     output), cos / sin [rows, D/2] fp32 (ops.llm.rope_tables), pos int32 [B]
     on the device.  Rotates q and k at position pos[b] with the convention
     and the roundings of ops.llm.rope_qkv, returns q [B, Hq, D] and stores k
     and v into slot pos[b] of the caches [B, Hkv, C, D]; no other slot is
-    written.  Positions are the caller's (KVCache.positions): a position
-    outside the cache or the table writes nothing on the GPU."""
-    _check_heads(Hq, Hkv, D)
-    B = qkv.shape[0]
-    if qkv.dim() != 2 or qkv.shape[1] != (Hq + 2 * Hkv) * D:
-        raise ValueError(f"qkv {tuple(qkv.shape)} is not [B, (Hq + 2 Hkv) D = {(Hq + 2 * Hkv) * D}]")
-    _check_cache(k_cache, v_cache, B, Hkv, D, qkv)
-    pos = _check_rows("pos", pos, B, qkv.device)
-    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.dtype != torch.float32:
-        raise ValueError(f"cos / sin {tuple(cos.shape)} {cos.dtype} are not fp32 [rows, D/2 = {D // 2}]")
-    C = k_cache.shape[2]
+    written.  Positions are the caller's (KVCache.positions, which never
+    leaves the cache): a position outside the cache or the table writes
+    nothing to the caches and a zero q row, as in rope_append_many."""
+    (pos,) = _check_rope(qkv, False, cos, sin, {"pos": pos}, k_cache, v_cache, Hq, Hkv, D)
+    B, C = qkv.shape[0], k_cache.shape[2]
     if _lib.use_hip(qkv):
-        if qkv.dtype != torch.bfloat16:
-            raise RuntimeError(f"HIP rope_append needs bf16 (got {qkv.dtype})")
+        _need_bf16("rope_append", qkv)
         qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
         q = torch.empty(B, Hq, D, device=qkv.device, dtype=qkv.dtype)
         _lib.call("toa_decode_rope_append", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(pos), _lib.ptr(q),
                   _lib.ptr(k_cache), _lib.ptr(v_cache), B, Hq, Hkv, D, C, cos.shape[0], _lib.stream(qkv))
         return q
-    p = pos.long()
-    x = qkv.view(B, Hq + 2 * Hkv, D)
-    d2 = D // 2
-    x1, x2 = x[:, :Hq + Hkv, :d2].float(), x[:, :Hq + Hkv, d2:].float()
-    c, s = cos[p][:, None], sin[p][:, None]
-    r = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(qkv.dtype)
-    rows = torch.arange(B)
-    k_cache[rows, :, p] = r[:, Hq:]
-    v_cache[rows, :, p] = x[:, Hq + Hkv:]
-    return r[:, :Hq].contiguous()
+    return _rope_ref(qkv[:, None], cos, sin, pos, None, k_cache, v_cache, Hq, Hkv, D)[:, 0]
 
 
 def decode_ws_floats(B, Hq, D, max_len, split_keys) -> int:
@@ -241,39 +309,19 @@ def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_l
     sizes the grid -- nothing is read back from the device.  A row's result
     depends on that row's q, cache, length and split_keys only."""
     split = check_split_keys(split_keys)
-    if q.dim() != 3:
-        raise ValueError(f"q {tuple(q.shape)} is not [B, Hq, D]")
+    (lengths,), max_len, scale = _check_attn(q, False, k_cache, v_cache, {"lengths": lengths}, max_len, scale)
     B, Hq, D = q.shape
-    if k_cache.dim() != 4:
-        raise ValueError(f"k_cache {tuple(k_cache.shape)} is not [B, Hkv, C, D]")
     Hkv, C = k_cache.shape[1], k_cache.shape[2]
-    _check_heads(Hq, Hkv, D)
-    _check_cache(k_cache, v_cache, B, Hkv, D, q)
-    lengths = _check_rows("lengths", lengths, B, q.device)
-    max_len = C if max_len is None else int(max_len)
-    if not 1 <= max_len <= C:
-        raise ValueError(f"max_len {max_len} outside 1 .. capacity {C}")
-    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     if _lib.use_hip(q):
-        if q.dtype != torch.bfloat16:
-            raise RuntimeError(f"HIP attn_decode needs bf16 (got {q.dtype})")
+        _need_bf16("attn_decode", q)
         q = q.contiguous()
         ws = torch.empty(decode_ws_floats(B, Hq, D, max_len, split), device=q.device, dtype=torch.float32)
         o = torch.empty_like(q)
         _lib.call("toa_attn_decode", _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(lengths),
                   _lib.ptr(ws), _lib.ptr(o), B, Hq, Hkv, C, D, max_len, split, scale, _lib.stream(q))
         return o
-    rep = Hq // Hkv
-    out = torch.zeros(B, Hq, D, dtype=q.dtype)
-    for b, n in enumerate(lengths.tolist()):
-        n = min(n, max_len)
-        if n < 1:
-            continue
-        k = k_cache[b, :, :n].float().repeat_interleave(rep, 0)     # [Hq, n, D]
-        v = v_cache[b, :, :n].float().repeat_interleave(rep, 0)
-        s = torch.matmul(k, q[b].float()[:, :, None]).squeeze(-1) * scale
-        out[b] = torch.matmul(torch.softmax(s, -1)[:, None], v).squeeze(1).to(q.dtype)
-    return out
+    # one token per row at the last of its keys, the lengths cut to the cache as the kernel cuts them
+    return _attn_ref(q[:, None], k_cache, v_cache, lengths.clamp(max=C) - 1, None, max_len, scale)[:, 0]
 
 
 # ---- extending the cache by T tokens per row (csrc/hip/extend.hip; docs/kernels.md "Extending the cache")
@@ -313,40 +361,18 @@ def rope_append_many(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D):
     slot of the caches [B, Hkv, C, D]; returns q [B, T, Hq, D].  A token with
     t >= count[b], or whose position is outside the cache or the table, writes
     nothing to the caches and a zero q row."""
-    _check_heads(Hq, Hkv, D)
-    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] != (Hq + 2 * Hkv) * D:
-        raise ValueError(f"qkv {tuple(qkv.shape)} is not [B, T >= 1, (Hq + 2 Hkv) D = {(Hq + 2 * Hkv) * D}]")
+    start, count = _check_rope(qkv, True, cos, sin, {"start": start, "count": count}, k_cache, v_cache, Hq, Hkv, D)
     B, T = qkv.shape[:2]
-    _check_cache(k_cache, v_cache, B, Hkv, D, qkv)
-    start = _check_rows("start", start, B, qkv.device)
-    count = _check_rows("count", count, B, qkv.device)
-    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.dtype != torch.float32:
-        raise ValueError(f"cos / sin {tuple(cos.shape)} {cos.dtype} are not fp32 [rows, D/2 = {D // 2}]")
     C = k_cache.shape[2]
     if _lib.use_hip(qkv):
-        if qkv.dtype != torch.bfloat16:
-            raise RuntimeError(f"HIP rope_append_many needs bf16 (got {qkv.dtype})")
+        _need_bf16("rope_append_many", qkv)
         qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
         q = torch.empty(B, T, Hq, D, device=qkv.device, dtype=qkv.dtype)
         _lib.call("toa_extend_rope_append", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(start),
                   _lib.ptr(count), _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), B, T, Hq, Hkv, D, C,
                   cos.shape[0], _lib.stream(qkv))
         return q
-    q = torch.zeros(B, T, Hq, D, dtype=qkv.dtype)
-    x = qkv.view(B, T, Hq + 2 * Hkv, D)
-    d2 = D // 2
-    for b, (s, n) in enumerate(zip(start.tolist(), count.tolist())):
-        n = min(n, T, C - s, cos.shape[0] - s) if s >= 0 else 0
-        if n < 1:
-            continue
-        xb = x[b, :n]
-        x1, x2 = xb[:, :Hq + Hkv, :d2].float(), xb[:, :Hq + Hkv, d2:].float()
-        c, sn = cos[s:s + n, None], sin[s:s + n, None]
-        r = torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn], -1).to(qkv.dtype)     # [n, Hq + Hkv, D]
-        q[b, :n] = r[:, :Hq]
-        k_cache[b, :, s:s + n] = r[:, Hq:].transpose(0, 1)
-        v_cache[b, :, s:s + n] = xb[:, Hq + Hkv:].transpose(0, 1)
-    return q
+    return _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D)
 
 
 def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, max_len=None, workspace=None):
@@ -364,19 +390,10 @@ def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, 
     depends on its q row, its cache row's keys 0 .. position, the position
     and split_keys only -- not on T, its index in the call, count, max_len or
     the batch."""
-    if q.dim() != 4 or q.shape[1] < 1:
-        raise ValueError(f"q {tuple(q.shape)} is not [B, T >= 1, Hq, D]")
+    (start, count), max_len, scale = _check_attn(q, True, k_cache, v_cache, {"start": start, "count": count}, max_len,
+                                                 scale)
     B, T, Hq, D = q.shape
-    if k_cache.dim() != 4:
-        raise ValueError(f"k_cache {tuple(k_cache.shape)} is not [B, Hkv, C, D]")
     Hkv, C = k_cache.shape[1], k_cache.shape[2]
-    _check_heads(Hq, Hkv, D)
-    _check_cache(k_cache, v_cache, B, Hkv, D, q)
-    start = _check_rows("start", start, B, q.device)
-    count = _check_rows("count", count, B, q.device)
-    max_len = C if max_len is None else int(max_len)
-    if not 1 <= max_len <= C:
-        raise ValueError(f"max_len {max_len} outside 1 .. capacity {C}")
     split = check_extend_split(extend_split(B, T, Hq, Hkv, max_len) if split_keys is None else split_keys)
     words = extend_ws_floats(B, T, Hq, D, max_len, split)
     if workspace is not None:
@@ -384,10 +401,8 @@ def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, 
                 or workspace.numel() < words or workspace.data_ptr() % 16):
             raise ValueError(f"workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {words} words "
                              f"on {q.device} (got {workspace.dtype} x {workspace.numel()} on {workspace.device})")
-    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     if _lib.use_hip(q):
-        if q.dtype != torch.bfloat16:
-            raise RuntimeError(f"HIP attn_extend needs bf16 (got {q.dtype})")
+        _need_bf16("attn_extend", q)
         q = q.contiguous()
         ws = torch.empty(words, device=q.device, dtype=torch.float32) if workspace is None else workspace
         o = torch.empty_like(q)
@@ -395,15 +410,4 @@ def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, 
                   _lib.ptr(count), _lib.ptr(ws), _lib.ptr(o), B, T, Hq, Hkv, C, D, max_len, split, scale,
                   _lib.stream(q))
         return o
-    rep = Hq // Hkv
-    out = torch.zeros(B, T, Hq, D, dtype=q.dtype)
-    for b, (s, cnt) in enumerate(zip(start.tolist(), count.tolist())):
-        if s < 0:
-            continue
-        kb = k_cache[b].float().repeat_interleave(rep, 0)     # [Hq, C, D]
-        vb = v_cache[b].float().repeat_interleave(rep, 0)
-        for t in range(min(cnt, T, C - s)):
-            n = min(s + t + 1, max_len)
-            sc = torch.matmul(kb[:, :n], q[b, t].float()[:, :, None]).squeeze(-1) * scale
-            out[b, t] = torch.matmul(torch.softmax(sc, -1)[:, None], vb[:, :n]).squeeze(1).to(q.dtype)
-    return out
+    return _attn_ref(q, k_cache, v_cache, start, count, max_len, scale)

@@ -729,6 +729,14 @@ extern "C" int toa_cast_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStr
 // frees.  mode 0: CUs 0 .. n-1 of the mask; mode 1: n CUs spread evenly over
 // the mask (which bit is which XCD is the driver's mapping: the probe
 // scripts/cu_mask_probe.py measures both).
+//
+// Where the runtime cannot make a queue with a CU mask (a virtual machine's
+// GPU), hipExtStreamCreateWithCUMask answers hipErrorOutOfMemory to a valid
+// mask: the launcher returns hipErrorNotSupported for it, so that the caller
+// can tell a GPU without the facility from bad arguments.  A failed create
+// also stays behind as the thread's last error, where the next launch check
+// (torch's, after any kernel) would report it as its own: it is cleared here,
+// since the return value carries it.
 // ---------------------------------------------------------------------------
 extern "C" int toa_stream_create_cu_mask(int mode, int n, void** out) {
   int dev = 0;
@@ -747,7 +755,10 @@ extern "C" int toa_stream_create_cu_mask(int mode, int n, void** out) {
   }
   hipStream_t s = nullptr;
   e = hipExtStreamCreateWithCUMask(&s, (uint32_t)words, mask);
-  if (e != hipSuccess) return (int)e;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return (int)(e == hipErrorOutOfMemory ? hipErrorNotSupported : e);
+  }
   *out = (void*)s;
   return 0;
 }

@@ -131,12 +131,25 @@ def check_skip_limit(skip_nonfinite: bool, skip_grad_norm) -> float:
 _MASKED = []   # (ExternalStream, handle): kept for the process's life
 
 
+HIP_ERROR_NOT_SUPPORTED = 801
+
+
+class MaskedStreamUnsupported(RuntimeError):
+    """This GPU's runtime makes no stream with a CU mask (a virtual machine's
+    GPU: the launcher's hipErrorNotSupported)."""
+
+
 def masked_stream(n: int, mode: int = 1, device=None):
     """A torch stream over a HIP stream whose kernels may use only `n` CUs
     (csrc/hip/optim.hip toa_stream_create_cu_mask; mode 1 spreads them over
-    the mask, mode 0 takes the first n)."""
+    the mask, mode 0 takes the first n).  MaskedStreamUnsupported where the
+    runtime has no such streams; RuntimeError for bad arguments."""
     h = ctypes.c_void_p()
-    _lib.call("toa_stream_create_cu_mask", int(mode), int(n), ctypes.byref(h))
+    rc = _lib.call_ret("toa_stream_create_cu_mask", int(mode), int(n), ctypes.byref(h))
+    if rc == HIP_ERROR_NOT_SUPPORTED:
+        raise MaskedStreamUnsupported("toa_stream_create_cu_mask: this GPU's runtime makes no stream with a CU mask")
+    if rc != 0:
+        raise RuntimeError(f"toa_stream_create_cu_mask failed with hipError {rc}")
     st = torch.cuda.ExternalStream(h.value, device=device)
     _MASKED.append((st, h))
     return st

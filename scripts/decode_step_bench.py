@@ -22,7 +22,8 @@ whatever the host's launch cost leaves exposed.
 
 One JSON line.
 
-    python scripts/decode_step_bench.py [--iters 50] [--rounds 8] [--skip-step] [--skip-forms]
+    python scripts/decode_step_bench.py [--iters 50] [--rounds 8] [--skip-step] [--skip-forms] [--only-stream]
+                                        [--extend]
 """
 import argparse
 import json
@@ -39,6 +40,7 @@ ROTATION_BYTES = 512 << 20
 FORMS = (("qkv", 6144, 4096, False), ("attn_out", 4096, 4096, False), ("gate_up", 14336, 4096, True),
          ("down", 4096, 14336, False), ("head", 128256, 4096, False))   # (name, N or F, K, SwiGLU)
 MS = (1, 8, 16)
+STREAM_MS = (17, 32, 48, 64)   # the 17-to-64-row kernel (csrc/hip/gemm_stream.hip): the ``stream`` arm against ``tile``
 STEPS = 16          # decode steps per arm visit of the whole-step ABBA
 
 
@@ -90,7 +92,32 @@ def bench_forms(a, dev):
         ws_name = "toa_gemm_skinny_swiglu_ws_bytes" if swiglu else "toa_gemm_skinny_ws_bytes"
         wsb = int(_lib.call_ret(ws_name, N, K))
         ws = torch.empty(max(wsb, 16) // 4, device=dev, dtype=torch.float32)
-        for M in MS:
+        st_wsb = int(_lib.call_ret(ws_name.replace("skinny", "stream"), N, K))
+        st_ws = torch.empty(max(st_wsb, 16) // 4, device=dev, dtype=torch.float32)
+        res["stream_split"] = _lib.call_ret("toa_gemm_stream_split", N, K)
+        for M in STREAM_MS if name != "head" else ():   # the head stays on the tile kernel (ops.decode.TILE_KEEPS_FROM)
+            x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            gu = torch.empty(M, 2 * N, device=dev, dtype=torch.bfloat16) if swiglu else None
+            wp = [P(w) for w in ws_]
+            sn_ = "toa_gemm_stream_swiglu" if swiglu else "toa_gemm_stream"
+
+            def stream(i):
+                _lib.call(sn_, P(x), K, wp[i % copies], K, P(y), N, M, N, K, P(st_ws), st)
+
+            def tile_(i):
+                if swiglu:
+                    _lib.call("toa_gemm_asm_swiglu", P(x), K, wp[i % copies], K, P(gu), 2 * N, P(y), N, M, N, K, st)
+                else:
+                    _lib.call("toa_gemm_asm_rows", P(x), K, wp[i % copies], K, P(y), N, M, N, K, st)
+
+            arms = {}
+            for arm, fn in (("stream", stream), ("tile", tile_)):
+                med, lo, hi = _sample_ms(fn, a.warmup, a.iters)
+                arms[arm] = _row(med, lo, hi, nbytes, copy_med)
+            arms["stream_vs_tile"] = round(arms["tile"]["median_us"] / arms["stream"]["median_us"], 3)
+            res[f"M{M}"] = arms
+        for M in MS if not a.only_stream else ():
             x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
             y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
             gu = torch.empty(M, 2 * N, device=dev, dtype=torch.bfloat16) if swiglu else None
@@ -159,6 +186,43 @@ def bench_step(a, dev):
     return out
 
 
+def bench_extend(a, dev):
+    """Llama.extend of T = 4 tokens on B = 8 rows at cache length --len, logits="last": ``tile`` and ``stream``
+    alternated ABBA, device events around each call; ms per call."""
+    from tf_operator_amd.models.llama import PRESETS, Llama
+
+    m = Llama(PRESETS["llama3-8b"], device=dev)
+    m.init_weights(0)
+    m.eval()
+    B, T = 8, 4
+    cache = m.new_cache(B, a.length + T)
+    tokens = torch.randint(0, m.cfg.vocab_size, (B, T), device=dev)
+
+    def visit(arm):
+        cache.set_lengths([a.length] * B)
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        with torch.no_grad():
+            m.extend(tokens, cache, gemm=arm, logits="last")
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e)
+
+    for arm in ("tile", "stream", "tile", "stream"):
+        visit(arm)   # warm-up: code objects, workspaces, allocator
+    t, s, d = [], [], []
+    for _ in range(a.rounds):
+        r = [visit(arm) for arm in ("tile", "stream", "stream", "tile")]
+        t.append((r[0] + r[3]) / 2)
+        s.append((r[1] + r[2]) / 2)
+        d.append(t[-1] - s[-1])
+    se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
+    return {"preset": "llama3-8b", "B": B, "T": T, "length": a.length, "rounds": a.rounds,
+            "tile_ms": round(statistics.mean(t), 4), "stream_ms": round(statistics.mean(s), 4),
+            "tile_minus_stream_ms": round(statistics.mean(d), 4), "stderr_ms": round(se, 4)}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=10)
@@ -167,6 +231,8 @@ def main(argv=None):
     ap.add_argument("--len", type=int, default=1024, dest="length")
     ap.add_argument("--skip-forms", action="store_true")
     ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--only-stream", action="store_true", help="per form, only the 17-to-64-row arms")
+    ap.add_argument("--extend", action="store_true", help="the whole extend call, tile against stream")
     a = ap.parse_args(argv)
     if a.iters < 50 or a.rounds < 8:
         ap.error("--iters must be at least 50 and --rounds at least 8")
@@ -182,6 +248,8 @@ def main(argv=None):
         res["forms"] = bench_forms(a, dev)
     if not a.skip_step:
         res["step"] = bench_step(a, dev)
+    if a.extend:
+        res["extend"] = bench_extend(a, dev)
     print(json.dumps(res))
 
 

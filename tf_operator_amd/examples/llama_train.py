@@ -57,9 +57,9 @@ def main(argv=None):
                         "decoding) and prints one JSON line {\"sample\": {\"step\", \"tokens\"}}; 0 = never")
     p.add_argument("--sample-tokens", type=int, default=16, metavar="M", help="new tokens per sample")
     p.add_argument("--sample-prompt-len", type=int, default=8, metavar="P", help="prompt tokens per sample")
-    p.add_argument("--sample-gemm", choices=["tile", "skinny"], default=None,
+    p.add_argument("--sample-gemm", choices=["tile", "skinny", "stream"], default=None,
                    help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
-                        "weight-streaming GEMM for 1 to 16 rows (skinny); default: TOA_DECODE_GEMM, else tile")
+                        "weight-streaming GEMM for 1 to 16 rows (skinny), or that and its 17-to-64-row twin (stream); default: TOA_DECODE_GEMM, else tile")
     p.add_argument("--sample-prefill-chunk", type=int, default=None, metavar="N",
                    help="prefill a sample's prompt N tokens at a time through the cache-extend kernels instead of all "
                         "at once through the training ops; default: all at once")

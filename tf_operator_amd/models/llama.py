@@ -236,7 +236,8 @@ class Llama(torch.nn.Module):
         layer's rotated K and V into the cache and return the logits [B, V] of
         position lengths[b]-1.  Causality keeps the pads out of every valid
         position, and cache slots at or beyond lengths[b] are never read.
-        gemm: as in decode_step; here only the head GEMM on the B last
+        gemm: as in decode_step (``stream`` serves chunks of 17 to 64 rows,
+        B x chunk, as well); here only the head GEMM on the B last
         positions' rows changes.
 
         chunk=n >= 1: the prompts go through :meth:`extend` n tokens at a
@@ -290,7 +291,8 @@ class Llama(torch.nn.Module):
         anything between a chunk of a prompt, a second turn, or drafted tokens
         to verify.  Embedding, norms and projections run on the B T rows
         (ops.decode.project / mlp by `gemm`, as in decode_step: the skinny
-        GEMM applies by its own check when B T <= 16, refused operands take
+        GEMM applies by its own check when B T <= 16 and, under ``stream``,
+        the 17-to-64-row GEMM when B T is 17 to 64; refused operands take
         ``tile`` and are counted), RoPE + append and the attention are
         ops.decode.rope_append_many / attn_extend (split_keys: None is
         ops.decode.extend_split's choice).
@@ -340,7 +342,9 @@ class Llama(torch.nn.Module):
         ``tile``: the training GEMMs (ops.linear.linear, swiglu_mlp);
         ``skinny``: the weight-streaming GEMM for 1 to 16 rows (ops.gemm
         linear_skinny / swiglu_skinny), the tile path for operands it
-        refuses; None: TOA_DECODE_GEMM, default ``tile``.  Anything else
+        refuses; ``stream``: ``skinny``, and for B of 17 to 64 rows the
+        weight-streaming GEMM that stages x in LDS (linear_stream /
+        swiglu_stream); None: TOA_DECODE_GEMM, default ``tile``.  Anything else
         raises ValueError before a launch."""
         cfg = self.cfg
         (B,) = tokens.shape

@@ -185,6 +185,13 @@ _SIGS = {
     "toa_gemm_skinny_split": [c_int, c_int],
     "toa_gemm_skinny_slice_steps": [c_int, c_int],
     "toa_gemm_skinny_set_nt": [c_int],
+    # 17 to 64 rows (csrc/hip/gemm_stream.hip, csrc/hip/gemm_stream_shapes.h): the skinny launchers' arguments
+    "toa_gemm_stream": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_stream_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_stream_check": [c_int] + [c_p] * 4 + [c_i64] * 4 + [c_int] * 3,
+    "toa_gemm_stream_split": [c_int, c_int],
+    "toa_gemm_stream_piece_chunks": [c_int, c_int],
+    "toa_gemm_stream_constant": [c_int],
 }
 
 
@@ -225,13 +232,15 @@ def _load():
         sw = getattr(lib, "toa_gemm_shape_why", None)
         if sw is not None:
             sw.argtypes, sw.restype = [c_int], ctypes.c_char_p
-        for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes"):
+        for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_stream_ws_bytes",
+                     "toa_gemm_stream_swiglu_ws_bytes"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
-        kw = getattr(lib, "toa_gemm_skinny_why", None)
-        if kw is not None:
-            kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
+        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why"):
+            kw = getattr(lib, name, None)
+            if kw is not None:
+                kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
         _lib = lib
 
 
@@ -259,7 +268,8 @@ def has(name: str) -> bool:
 # launchers whose argument / result types _load sets outside _SIGS
 _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coherent_alloc", "toa_wgrad_workspace",
                     "toa_wgrad_asm_workspace", "toa_gemm_shape_why", "toa_gemm_skinny_ws_bytes",
-                    "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why"}
+                    "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why", "toa_gemm_stream_ws_bytes",
+                    "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why"}
 
 
 def _fn(name: str):

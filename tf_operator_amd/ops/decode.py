@@ -32,7 +32,7 @@ HEAD_DIMS = (64, 128)     # the kernels' head-dim instantiations (csrc/hip/decod
 SPLIT_KEYS_DEFAULT = 256
 
 
-GEMMS = ("tile", "skinny")   # what runs a decode step's projections (docs/kernels.md "Decoding")
+GEMMS = ("tile", "skinny", "stream")   # what runs a decode step's projections (docs/kernels.md "Decoding")
 # Under ``skinny``, a projection whose training GEMM already has a 256 x 256 tile per CU or more stays on it: at the
 # Llama-3-8B head (128256 x 4096, 501 tiles) the tile kernel measured 6 to 48 % faster than the skinny one at 1, 8 and
 # 16 rows on the same box; at the forms of 16 to 112 tiles it is 1.3 to 7.9 x slower (docs/kernels.md "Decoding").
@@ -54,13 +54,19 @@ def project(x, w, gemm="tile"):
     (the head of a large vocabulary: the tile kernel measured faster there);
     operands the skinny check refuses (more than 16 rows, a non-bf16 GPU
     model) take the tile path and are counted (ops.gemm.fallbacks, warned
-    once per shape)."""
-    if gemm == "skinny":
+    once per shape).  ``stream``: as ``skinny``, and operands of 17 to 64 rows
+    take ops.gemm.linear_stream; only what both checks refuse takes the tile
+    path and is counted."""
+    if gemm in ("skinny", "stream"):
         if w.shape[0] >= TILE_KEEPS_FROM and _gemm.asm_takes(x, w):
             return linear(x, w)   # the measured dispatch, not a fallback
         why = _gemm.skinny_refusal(x, w)
         if not why:
             return _gemm.linear_skinny(x, w)
+        if gemm == "stream":
+            why = _gemm.stream_refusal(x, w)
+            if not why:
+                return _gemm.linear_stream(x, w)
         _gemm._fallback("decode", (x.shape[0], w.shape[0], x.shape[1]), "tile", why)
     return linear(x, w)
 
@@ -69,11 +75,16 @@ def mlp(x, wgu, wd, gemm="tile"):
     """The Llama MLP of a decode step, x [B, H] -> [B, H].  ``skinny``: the
     SwiGLU in the gate|up GEMM (ops.gemm.swiglu_skinny: one launch, no
     [B, 2F] round trip), then the down projection; refused operands as in
-    :func:`project`."""
-    if gemm == "skinny":
+    :func:`project`.  ``stream``: the same, with ops.gemm.swiglu_stream for
+    17 to 64 rows."""
+    if gemm in ("skinny", "stream"):
         why = _gemm.skinny_refusal(x, wgu, swiglu=True)
         if not why:
             return project(_gemm.swiglu_skinny(x, wgu), wd, gemm)
+        if gemm == "stream":
+            why = _gemm.stream_refusal(x, wgu, swiglu=True)
+            if not why:
+                return project(_gemm.swiglu_stream(x, wgu), wd, gemm)
         _gemm._fallback("decode", (x.shape[0], wgu.shape[0], x.shape[1]), "tile", why)
     return swiglu_mlp(x, wgu, wd)
 

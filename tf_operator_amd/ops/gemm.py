@@ -508,17 +508,21 @@ def _workspace(dev, nbytes):
 # ---- 1 to 16 rows: the weight-streaming GEMM of the decode step (csrc/hip/gemm_skinny.hip).  What it takes is
 # csrc/hip/gemm_skinny_shapes.h's to say (toa_gemm_skinny_check); this module adds only what a launcher cannot see:
 # the tensors' kind.
+def _stream_reason(kind, x2, w, swiglu, y, ws) -> int:
+    M, K = x2.shape
+    N = w.shape[0] // 2 if swiglu else w.shape[0]
+    y_ptr, ldy = (x2.data_ptr(), N) if y is None else (y.data_ptr(), y.stride(0))
+    ws_ptr = x2.data_ptr() if ws is None else ws.data_ptr()
+    return _lib.call_ret(f"toa_gemm_{kind}_check", int(swiglu), x2.data_ptr(), w.data_ptr(), y_ptr, ws_ptr,
+                         x2.stride(0), w.stride(0), ldy, w.shape[0], M, N, K)
+
+
 def skinny_reason(x2, w, swiglu: bool = False, y=None, ws=None) -> int:
     """toa_gemm_skinny_check for y [M, N] = x2 [M, K] w [N, K]^T (swiglu: w =
     gate | up [2F, K], y = s [M, F]): 0 = taken, else the reason
     :func:`skinny_why` names.  y and ws default to what the launch wrappers
     allocate themselves (contiguous, aligned): x2 stands in for them."""
-    M, K = x2.shape
-    N = w.shape[0] // 2 if swiglu else w.shape[0]
-    y_ptr, ldy = (x2.data_ptr(), N) if y is None else (y.data_ptr(), y.stride(0))
-    ws_ptr = x2.data_ptr() if ws is None else ws.data_ptr()
-    return _lib.call_ret("toa_gemm_skinny_check", int(swiglu), x2.data_ptr(), w.data_ptr(), y_ptr, ws_ptr,
-                         x2.stride(0), w.stride(0), ldy, w.shape[0], M, N, K)
+    return _stream_reason("skinny", x2, w, swiglu, y, ws)
 
 
 def skinny_why(reason: int) -> str:
@@ -530,8 +534,12 @@ def skinny_refusal(x2, w, swiglu: bool = False) -> str:
     if they are: matrices with unit column stride and a common K, bf16 on the
     GPU (CPU tensors of any float dtype take the fp32 reference), and a shape
     the launcher's check takes, in its own words."""
-    if not _lib.has("toa_gemm_skinny_check"):
-        return "library built without toa_gemm_skinny"
+    return _stream_refusal("skinny", x2, w, swiglu)
+
+
+def _stream_refusal(kind, x2, w, swiglu) -> str:
+    if not _lib.has(f"toa_gemm_{kind}_check"):
+        return f"library built without toa_gemm_{kind}"
     for t in (x2, w):
         if t.dim() != 2:
             return f"a {t.dim()}-D tensor, not a matrix"
@@ -543,9 +551,9 @@ def skinny_refusal(x2, w, swiglu: bool = False) -> str:
         return f"x ({x2.dtype}, {x2.device}) and w ({w.dtype}, {w.device}) differ"
     if w.shape[1] != x2.shape[1]:
         return f"K={x2.shape[1]} columns against {w.shape[1]} in the weight"
-    r = skinny_reason(x2, w, swiglu)
+    r = _stream_reason(kind, x2, w, swiglu, None, None)
     if r:
-        return f"{skinny_why(r)}: M={x2.shape[0]} N={w.shape[0] // 2 if swiglu else w.shape[0]} K={x2.shape[1]}"
+        return f"{_lib._fn(f'toa_gemm_{kind}_why')(r).decode()}: M={x2.shape[0]} N={w.shape[0] // 2 if swiglu else w.shape[0]} K={x2.shape[1]}"
     return ""
 
 
@@ -554,8 +562,8 @@ def skinny_takes(x2, w, swiglu: bool = False) -> bool:
     return x2.is_cuda and w.is_cuda and not skinny_refusal(x2, w, swiglu)
 
 
-def _skinny_call(name, ws_name, x2, w, N, swiglu):
-    r = skinny_refusal(x2, w, swiglu)
+def _skinny_call(name, ws_name, x2, w, N, swiglu, kind="skinny"):
+    r = _stream_refusal(kind, x2, w, swiglu)
     if r:
         raise ValueError(f"{name}: {r}")
     M, K = x2.shape
@@ -585,6 +593,52 @@ def swiglu_skinny(x2: torch.Tensor, wgu: torch.Tensor) -> torch.Tensor:
     reading(wgu, "swiglu_skinny")
     F_ = wgu.shape[0] // 2
     s = _skinny_call("toa_gemm_skinny_swiglu", "toa_gemm_skinny_swiglu_ws_bytes", x2, wgu, F_, True)
+    if s is None:
+        gu = x2.float() @ wgu.float().t()
+        s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
+    return s
+
+
+# ---- 17 to 64 rows: the weight-streaming GEMM with x in LDS (csrc/hip/gemm_stream.hip; what it takes is
+# csrc/hip/gemm_stream_shapes.h's to say).  Twins of the functions above.
+def stream_reason(x2, w, swiglu: bool = False, y=None, ws=None) -> int:
+    """toa_gemm_stream_check, as :func:`skinny_reason`: 0 = taken, else the
+    reason :func:`stream_why` names."""
+    return _stream_reason("stream", x2, w, swiglu, y, ws)
+
+
+def stream_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_stream_why")(reason).decode()
+
+
+def stream_refusal(x2, w, swiglu: bool = False) -> str:
+    """Why (x2 [M, K], w [N, K]) are no operands of the 17-to-64-row GEMM, ""
+    if they are; the rules of :func:`skinny_refusal`, the launcher's own
+    words for the shape."""
+    return _stream_refusal("stream", x2, w, swiglu)
+
+
+def stream_takes(x2, w, swiglu: bool = False) -> bool:
+    """bf16 GPU matrices with unit column stride whose shape toa_gemm_stream_check accepts."""
+    return x2.is_cuda and w.is_cuda and not stream_refusal(x2, w, swiglu)
+
+
+def linear_stream(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """y [M, N] = x2 [M, K] w [N, K]^T for 17 <= M <= 64 on toa_gemm_stream:
+    fp32 accumulation, one rounding.  Operands stream_refusal names raise
+    ValueError before a launch; CPU tensors take the fp32 reference."""
+    reading(w, "linear_stream")
+    y = _skinny_call("toa_gemm_stream", "toa_gemm_stream_ws_bytes", x2, w, w.shape[0], False, "stream")
+    return (x2.float() @ w.float().t()).to(x2.dtype) if y is None else y
+
+
+def swiglu_stream(x2: torch.Tensor, wgu: torch.Tensor) -> torch.Tensor:
+    """s [M, F] = silu(x2 Wg^T) * (x2 Wu^T), wgu = gate | up [2F, K], for
+    17 <= M <= 64 on toa_gemm_stream_swiglu: the product is taken from the
+    fp32 accumulators and rounded once; gu is never stored."""
+    reading(wgu, "swiglu_stream")
+    F_ = wgu.shape[0] // 2
+    s = _skinny_call("toa_gemm_stream_swiglu", "toa_gemm_stream_swiglu_ws_bytes", x2, wgu, F_, True, "stream")
     if s is None:
         gu = x2.float() @ wgu.float().t()
         s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)

@@ -49,7 +49,8 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     synchronises with the host.  capacity: the KV cache's (default: P +
     max_new_tokens); too small a one raises ValueError before any launch.
     gemm: what runs the projections of the decode steps and the prefill's head
-    (Llama.decode_step; None: TOA_DECODE_GEMM, default ``tile``).
+    (Llama.decode_step: ``tile``, ``skinny`` or ``stream``; None:
+    TOA_DECODE_GEMM, default ``tile``).
     prefill_chunk: Llama.prefill's chunk (None: the whole prompt at once
     through the training ops; n >= 1: n tokens at a time through the
     cache-extend kernels).

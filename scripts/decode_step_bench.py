@@ -22,8 +22,12 @@ whatever the host's launch cost leaves exposed.
 
 One JSON line.
 
+``--fp8``: the 1-to-16-row GEMM on fp8 weights (csrc/hip/gemm_w8.hip) beside
+``skinny``, per form against a copy of q's bytes and as a whole step on a
+snapshot (bench_fp8).
+
     python scripts/decode_step_bench.py [--iters 50] [--rounds 8] [--skip-step] [--skip-forms] [--only-stream]
-                                        [--extend]
+                                        [--extend] [--fp8]
 """
 import argparse
 import json
@@ -186,6 +190,99 @@ def bench_step(a, dev):
     return out
 
 
+def bench_fp8(a, dev):
+    """The fp8 arm (csrc/hip/gemm_w8.hip) beside ``skinny``.  Per form, the four block projections at M = 1, 8 and
+    16: the fp8 GEMM over rotating copies of q (at least ROTATION_BYTES of them), the bf16 skinny GEMM over as many
+    copies of W, and a device copy of q's bytes as the yardstick.  Whole step: ``decode_step(gemm="skinny")`` on the
+    bf16 weights against the same on a snapshot, ABBA as in bench_step; the time of quantize_projections and the
+    snapshot's bytes."""
+    from tf_operator_amd.models.llama import PRESETS, Llama
+    from tf_operator_amd.ops import _lib, gemm
+
+    P, st = _lib.ptr, _lib.stream()
+    forms = {}
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, swiglu in FORMS[:4]:
+        rows = 2 * N if swiglu else N
+        qbytes = rows * K
+        copies = max(2, -(-ROTATION_BYTES // qbytes))
+        ws_ = [(torch.randn(rows, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        pairs = [gemm.quantize_w8(w) for w in ws_]
+        dst = torch.empty_like(pairs[0][0])
+        res = {"N": N, "K": K, "swiglu": swiglu, "q_bytes": qbytes, "copies": copies,
+               "split": _lib.call_ret("toa_gemm_skinny_w8_split", rows, K),
+               "skinny_split": _lib.call_ret("toa_gemm_skinny_split", N, K)}
+        copy_med, lo, hi = _sample_ms(lambda i: dst.copy_(pairs[i % copies][0]), a.warmup, a.iters)
+        res["copy_q"] = _row(copy_med, lo, hi, qbytes)
+        tail = "_swiglu" if swiglu else ""
+        ws8 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny_w8{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        ws16 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        wp, qp, sp = [P(w) for w in ws_], [P(q) for q, _ in pairs], [P(s) for _, s in pairs]
+        for M in MS:
+            x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+
+            def fp8(i):
+                _lib.call("toa_gemm_skinny_w8" + tail, P(x), K, qp[i % copies], K, sp[i % copies], P(y), N, M, N, K,
+                          P(ws8), st)
+
+            def skinny(i):
+                _lib.call("toa_gemm_skinny" + tail, P(x), K, wp[i % copies], K, P(y), N, M, N, K, P(ws16), st)
+
+            arms = {"fp8": _row(*_sample_ms(fp8, a.warmup, a.iters), qbytes, copy_med),
+                    "skinny": _row(*_sample_ms(skinny, a.warmup, a.iters), 2 * qbytes)}
+            arms["fp8_vs_skinny"] = round(arms["skinny"]["median_us"] / arms["fp8"]["median_us"], 3)
+            res[f"M{M}"] = arms
+        forms[name] = res
+        del ws_, pairs, dst
+        torch.cuda.empty_cache()
+    out = {"forms": forms}
+    if a.skip_step:
+        return out
+    m = Llama(PRESETS["llama3-8b"], device=dev)
+    m.init_weights(0)
+    m.eval()
+    m.quantize_projections()   # warm-up
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    snap = m.quantize_projections()
+    e.record()
+    e.synchronize()
+    step = {"preset": "llama3-8b", "length": a.length, "steps_per_visit": STEPS, "rounds": a.rounds,
+            "quantize_projections_ms": round(s.elapsed_time(e), 3),
+            "snapshot_bytes": sum(q.numel() + 4 * sc.numel() for b in snap for q, sc in b.values())}
+    for B in (1, 8):
+        cache = m.new_cache(B, a.length + STEPS)
+        tokens = torch.randint(0, m.cfg.vocab_size, (B,), device=dev)
+
+        def visit(weights):
+            cache.set_lengths([a.length] * B)
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(STEPS):
+                m.decode_step(tokens, cache, gemm="skinny", weights=weights)
+            e.record()
+            e.synchronize()
+            return s.elapsed_time(e) / STEPS
+
+        for w in (None, snap):
+            visit(w)   # warm-up: code objects, workspaces, allocator
+        t, f, d = [], [], []
+        for _ in range(a.rounds):
+            r = [visit(w) for w in (None, snap, snap, None)]
+            t.append((r[0] + r[3]) / 2)
+            f.append((r[1] + r[2]) / 2)
+            d.append(t[-1] - f[-1])
+        se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
+        step[f"B{B}"] = {"skinny_ms_per_step": round(statistics.mean(t), 4), "fp8_ms_per_step": round(statistics.mean(f), 4),
+                         "skinny_minus_fp8_ms": round(statistics.mean(d), 4), "stderr_ms": round(se, 4)}
+    assert not [k for k in gemm.fallbacks() if k.startswith("decode")]
+    out["step"] = step
+    return out
+
+
 def bench_extend(a, dev):
     """Llama.extend of T = 4 tokens on B = 8 rows at cache length --len, logits="last": ``tile`` and ``stream``
     alternated ABBA, device events around each call; ms per call."""
@@ -233,6 +330,8 @@ def main(argv=None):
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--only-stream", action="store_true", help="per form, only the 17-to-64-row arms")
     ap.add_argument("--extend", action="store_true", help="the whole extend call, tile against stream")
+    ap.add_argument("--fp8", action="store_true",
+                    help="only the fp8 arm beside skinny: per form, the whole step (unless --skip-step), the quantiser")
     a = ap.parse_args(argv)
     if a.iters < 50 or a.rounds < 8:
         ap.error("--iters must be at least 50 and --rounds at least 8")
@@ -244,9 +343,11 @@ def main(argv=None):
     gemm.resolve_auto()
     dev = torch.device("cuda", 0)
     res = {"device": torch.cuda.get_device_name(dev), "gemm_mode": gemm.mode(), "iters": a.iters, "inner": INNER}
-    if not a.skip_forms:
+    if a.fp8:
+        res["fp8"] = bench_fp8(a, dev)
+    if not a.skip_forms and not a.fp8:
         res["forms"] = bench_forms(a, dev)
-    if not a.skip_step:
+    if not a.skip_step and not a.fp8:
         res["step"] = bench_step(a, dev)
     if a.extend:
         res["extend"] = bench_extend(a, dev)

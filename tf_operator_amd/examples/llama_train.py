@@ -60,6 +60,9 @@ def main(argv=None):
     p.add_argument("--sample-gemm", choices=["tile", "skinny", "stream"], default=None,
                    help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
                         "weight-streaming GEMM for 1 to 16 rows (skinny), or that and its 17-to-64-row twin (stream); default: TOA_DECODE_GEMM, else tile")
+    p.add_argument("--sample-weights", choices=["bf16", "fp8"], default=None,
+                   help="what a sample's projections read: the bf16 weights, or an e4m3 copy quantised at the start of "
+                        "each sample (needs --sample-gemm skinny or stream); default: TOA_DECODE_WEIGHTS, else bf16")
     p.add_argument("--sample-prefill-chunk", type=int, default=None, metavar="N",
                    help="prefill a sample's prompt N tokens at a time through the cache-extend kernels instead of all "
                         "at once through the training ops; default: all at once")
@@ -129,7 +132,7 @@ def _sample(a, tr, tokens):
     P = a.sample_prompt_len
     out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm, prefill_chunk=a.sample_prefill_chunk,
                          temperature=a.sample_temperature, top_k=a.sample_top_k, top_p=a.sample_top_p,
-                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler)
+                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler, weights=a.sample_weights)
     print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
 
 

@@ -26,12 +26,15 @@ import torch
 
 from ..ops.decode import KVCache, attn_decode, check_gemm, check_split_keys, rope_append
 from ..ops import decode as _dec
+from ..ops import gemm as _gemm
 from ..ops.embedding import Embedding
 from ..ops.linear import linear
 from ..ops.llm import (attention_block, causal_attention, cross_entropy, rope_cossin, rope_qkv, rope_tables, swiglu_mlp,
                        swiglu_mlp_resadd_ok)
 from ..ops.norm import RMSNorm
 from ..parallel.zero_check import reading
+
+W8_NAMES = ("wqkv", "wo", "wgu", "wd")   # a block's projections that Llama.quantize_projections snapshots
 
 
 @dataclasses.dataclass
@@ -212,25 +215,50 @@ class Llama(torch.nn.Module):
         reading(head, "lm_head")
         return _dec.project(x, head, gemm)
 
-    def _cached_blocks(self, h, attend, gemm):
+    @torch.no_grad()
+    def quantize_projections(self):
+        """A snapshot of the blocks' projections on fp8 weights
+        (ops.gemm.quantize_w8: e4m3 with one power-of-two scale per row): per
+        block a dict of (q, scale) for ``wqkv``, ``wo``, ``wgu`` and ``wd``,
+        half the bytes of the bf16 weights.  decode_step, extend, prefill and
+        train.generate.generate take it as ``weights=``.  The head stays bf16.
+        It is a copy: weights updated after the call are not in it."""
+        for blk in self.blocks:
+            for n in W8_NAMES:
+                reading(getattr(blk, n), "quantize_projections")
+        return [{n: _gemm.quantize_w8(getattr(blk, n).detach()) for n in W8_NAMES} for blk in self.blocks]
+
+    def _check_weights(self, weights, gemm):
+        """weights=None, or a snapshot of this model under a weight-streaming `gemm`; else ValueError."""
+        if weights is None:
+            return
+        if gemm == "tile":
+            raise ValueError('weights: a snapshot needs gemm="skinny" or "stream"; gemm="tile" reads the bf16 weights')
+        if len(weights) != len(self.blocks) or any(set(b) != set(W8_NAMES) for b in weights):
+            raise ValueError(f"weights: not a snapshot of this model's {len(self.blocks)} blocks "
+                             f"(Llama.quantize_projections: {W8_NAMES} per block)")
+
+    def _cached_blocks(self, h, attend, gemm, weights=None):
         """The blocks over the rows h [n, hidden] for prefill, extend and
         decode_step, projections by `gemm` (ops.decode.project / mlp; ``tile``
-        is linear / swiglu_mlp).  attend(layer index, qkv [n, (Hq + 2 Hkv) D])
+        is linear / swiglu_mlp), on the fp8 pairs of `weights` where it is a
+        snapshot.  attend(layer index, qkv [n, (Hq + 2 Hkv) D])
         rotates, fills the layer's cache and returns the attention output
         [n, Hq D].  Returns the residual stream and the last delta."""
         delta = None
         for i, blk in enumerate(self.blocks):
+            w8 = weights[i] if weights is not None else dict.fromkeys(W8_NAMES)
             if delta is None:
                 x = blk.attn_norm(h)
             else:
                 h, x = blk.attn_norm(h, delta)
-            o = attend(i, _dec.project(x, blk.wqkv, gemm))
-            h, x = blk.mlp_norm(h, _dec.project(o, blk.wo, gemm))
-            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm)
+            o = attend(i, _dec.project(x, blk.wqkv, gemm, w8["wqkv"]))
+            h, x = blk.mlp_norm(h, _dec.project(o, blk.wo, gemm, w8["wo"]))
+            delta = _dec.mlp(x, blk.wgu, blk.wd, gemm, w8["wgu"], w8["wd"])
         return h, delta
 
     @torch.no_grad()
-    def prefill(self, tokens, cache, lengths=None, gemm=None, chunk=None):
+    def prefill(self, tokens, cache, lengths=None, gemm=None, chunk=None, weights=None):
         """Run the prompts tokens [B, P] (ragged ones right-padded; lengths:
         host ints, default P each) through the training ops, copy every
         layer's rotated K and V into the cache and return the logits [B, V] of
@@ -238,7 +266,9 @@ class Llama(torch.nn.Module):
         position, and cache slots at or beyond lengths[b] are never read.
         gemm: as in decode_step (``stream`` serves chunks of 17 to 64 rows,
         B x chunk, as well); here only the head GEMM on the B last
-        positions' rows changes.
+        positions' rows changes.  weights: as in decode_step; it serves the
+        chunks of chunk=n (the whole-prompt path runs the training GEMMs on
+        the bf16 weights).
 
         chunk=n >= 1: the prompts go through :meth:`extend` n tokens at a
         time instead (every projection by `gemm`), so the intermediates are
@@ -248,6 +278,7 @@ class Llama(torch.nn.Module):
         cfg = self.cfg
         B, P = tokens.shape
         gemm = check_gemm(gemm)
+        self._check_weights(weights, gemm)
         self._check_cache(cache, B)
         lengths = [P] * B if lengths is None else [int(n) for n in lengths]
         if len(lengths) != B or min(lengths) < 1 or max(lengths) > P:
@@ -261,7 +292,7 @@ class Llama(torch.nn.Module):
             logits = None
             for c0 in range(0, max(lengths), chunk):
                 counts = [min(max(n - c0, 0), chunk) for n in lengths]
-                lg = self.extend(tokens[:, c0:c0 + chunk], cache, counts, gemm=gemm)
+                lg = self.extend(tokens[:, c0:c0 + chunk], cache, counts, gemm=gemm, weights=weights)
                 if logits is None:
                     logits = lg
                 else:   # a row's logits come from the chunk that holds its last token
@@ -284,7 +315,7 @@ class Llama(torch.nn.Module):
         return self._logits_of(h, delta, last, gemm)
 
     @torch.no_grad()
-    def extend(self, tokens, cache, counts=None, split_keys=None, gemm=None, logits="last"):
+    def extend(self, tokens, cache, counts=None, split_keys=None, gemm=None, logits="last", weights=None):
         """Append counts[b] (host ints >= 0, not all zero; default T each) of
         the tokens [B, T] to row b of the cache at its current length: T = 1
         on a filled cache is a decode step, T = P on an empty one a prefill,
@@ -295,7 +326,7 @@ class Llama(torch.nn.Module):
         the 17-to-64-row GEMM when B T is 17 to 64; refused operands take
         ``tile`` and are counted), RoPE + append and the attention are
         ops.decode.rope_append_many / attn_extend (split_keys: None is
-        ops.decode.extend_split's choice).
+        ops.decode.extend_split's choice).  weights: as in decode_step.
 
         logits="last": [B, V] at each row's last new token; only those B rows
         go through the final norm and the head.  "all": [B, T, V].  The
@@ -307,6 +338,7 @@ class Llama(torch.nn.Module):
             raise ValueError(f"tokens {tuple(tokens.shape)} is not [B, T >= 1]")
         B, T = tokens.shape
         gemm = check_gemm(gemm)
+        self._check_weights(weights, gemm)
         self._check_cache(cache, B)
         if logits not in ("last", "all"):
             raise ValueError(f"logits={logits!r}: expected 'last' or 'all'")
@@ -325,14 +357,14 @@ class Llama(torch.nn.Module):
             o = _dec.attn_extend(q, cache.k[i], cache.v[i], start, count, split_keys=split_keys, max_len=max_len)
             return o.view(B * T, Hq * D)
 
-        h, delta = self._cached_blocks(self.embed(tokens).view(B * T, cfg.hidden), attend, gemm)
+        h, delta = self._cached_blocks(self.embed(tokens).view(B * T, cfg.hidden), attend, gemm, weights)
         if logits == "all":
             return self._logits_of(h, delta, gemm=gemm).view(B, T, -1)
         last = torch.tensor([b * T + max(n, 1) - 1 for b, n in enumerate(counts)], device=tokens.device)
         return self._logits_of(h[last], delta[last], gemm=gemm)
 
     @torch.no_grad()
-    def decode_step(self, tokens, cache, split_keys=None, gemm=None):
+    def decode_step(self, tokens, cache, split_keys=None, gemm=None, weights=None):
         """One new token per row, tokens [B], against the cache: appends the
         token's rotated K and V at each row's length and returns the logits
         [B, V] of that position.  No host synchronisation; past the cache's
@@ -345,10 +377,18 @@ class Llama(torch.nn.Module):
         refuses; ``stream``: ``skinny``, and for B of 17 to 64 rows the
         weight-streaming GEMM that stages x in LDS (linear_stream /
         swiglu_stream); None: TOA_DECODE_GEMM, default ``tile``.  Anything else
-        raises ValueError before a launch."""
+        raises ValueError before a launch.
+
+        weights: None, or a snapshot from :meth:`quantize_projections`: the
+        blocks' projections of up to 16 rows then run on the fp8 weights
+        (ops.gemm linear_skinny_w8 / swiglu_skinny_w8: half the weight bytes);
+        operands that GEMM refuses take the bf16 weight by `gemm` and are
+        counted (ops.gemm.fallbacks).  The head stays bf16.  A snapshot with
+        ``gemm="tile"`` raises ValueError."""
         cfg = self.cfg
         (B,) = tokens.shape
         gemm = check_gemm(gemm)
+        self._check_weights(weights, gemm)
         self._check_cache(cache, B)
         split_keys = check_split_keys(split_keys)
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
@@ -361,5 +401,5 @@ class Llama(torch.nn.Module):
             o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len)
             return o.view(B, Hq * D)
 
-        h, delta = self._cached_blocks(self.embed(tokens), attend, gemm)
+        h, delta = self._cached_blocks(self.embed(tokens), attend, gemm, weights)
         return self._logits_of(h, delta, gemm=gemm)

@@ -192,6 +192,16 @@ _SIGS = {
     "toa_gemm_stream_split": [c_int, c_int],
     "toa_gemm_stream_piece_chunks": [c_int, c_int],
     "toa_gemm_stream_constant": [c_int],
+    # fp8 weights, 1 to 16 rows (csrc/hip/gemm_w8.hip, csrc/hip/gemm_w8_shapes.h).  The quantiser: w ldw q ldq (bytes)
+    # scale, N K, stream.  The GEMMs: x ldx q ldw (bytes) scale y ldy, M N K, workspace, stream.  The check: form,
+    # x q y workspace scale, ldx ldw ldy, rows behind q, M N K
+    "toa_quant_w8": [c_p, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p],
+    "toa_gemm_skinny_w8": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_skinny_w8_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_skinny_w8_check": [c_int] + [c_p] * 5 + [c_i64] * 4 + [c_int] * 3,
+    "toa_gemm_skinny_w8_split": [c_int, c_int],
+    "toa_gemm_skinny_w8_slice_steps": [c_int, c_int],
+    "toa_gemm_skinny_w8_constant": [c_int],
 }
 
 
@@ -233,11 +243,12 @@ def _load():
         if sw is not None:
             sw.argtypes, sw.restype = [c_int], ctypes.c_char_p
         for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_stream_ws_bytes",
-                     "toa_gemm_stream_swiglu_ws_bytes"):
+                     "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_skinny_w8_ws_bytes",
+                     "toa_gemm_skinny_w8_swiglu_ws_bytes"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
-        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why"):
+        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -269,7 +280,8 @@ def has(name: str) -> bool:
 _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coherent_alloc", "toa_wgrad_workspace",
                     "toa_wgrad_asm_workspace", "toa_gemm_shape_why", "toa_gemm_skinny_ws_bytes",
                     "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why", "toa_gemm_stream_ws_bytes",
-                    "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why"}
+                    "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why", "toa_gemm_skinny_w8_ws_bytes",
+                    "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why"}
 
 
 def _fn(name: str):

@@ -47,7 +47,22 @@ def check_gemm(gemm) -> str:
     return g
 
 
-def project(x, w, gemm="tile"):
+def _w8(x, pair, swiglu, gemm):
+    """True when the fp8 pair (q, scale) of a weights snapshot serves these rows
+    (ops.gemm.skinny_w8_refusal: the launcher's own check).  Refused operands
+    -- more than 16 rows, say -- are counted (ops.gemm.fallbacks, warned once
+    per shape) and the caller goes on with the block's bf16 weight by `gemm`."""
+    if pair is None:
+        return False
+    if gemm == "tile":
+        raise ValueError('a weights snapshot needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
+    why = _gemm.skinny_w8_refusal(x, pair[0], pair[1], swiglu)
+    if why:
+        _gemm._fallback("decode-fp8", (x.shape[0], pair[0].shape[0], x.shape[1]), f"bf16 {gemm}", why)
+    return not why
+
+
+def project(x, w, gemm="tile", w8=None):
     """x [B, K] w [N, K]^T of a decode step.  ``tile``: ops.linear.linear, the
     training GEMMs.  ``skinny``: ops.gemm.linear_skinny, except from
     TILE_KEEPS_FROM rows of W on where the assembly GEMM takes the operands
@@ -56,7 +71,11 @@ def project(x, w, gemm="tile"):
     model) take the tile path and are counted (ops.gemm.fallbacks, warned
     once per shape).  ``stream``: as ``skinny``, and operands of 17 to 64 rows
     take ops.gemm.linear_stream; only what both checks refuse takes the tile
-    path and is counted."""
+    path and is counted.  w8: w's fp8 pair (q, scale) of a weights snapshot
+    (Llama.quantize_projections); operands its check takes run on
+    ops.gemm.linear_skinny_w8 and w is not read."""
+    if _w8(x, w8, False, gemm):
+        return _gemm.linear_skinny_w8(x, *w8, checked=True)
     if gemm in ("skinny", "stream"):
         if w.shape[0] >= TILE_KEEPS_FROM and _gemm.asm_takes(x, w):
             return linear(x, w)   # the measured dispatch, not a fallback
@@ -71,20 +90,23 @@ def project(x, w, gemm="tile"):
     return linear(x, w)
 
 
-def mlp(x, wgu, wd, gemm="tile"):
+def mlp(x, wgu, wd, gemm="tile", w8gu=None, w8d=None):
     """The Llama MLP of a decode step, x [B, H] -> [B, H].  ``skinny``: the
     SwiGLU in the gate|up GEMM (ops.gemm.swiglu_skinny: one launch, no
     [B, 2F] round trip), then the down projection; refused operands as in
     :func:`project`.  ``stream``: the same, with ops.gemm.swiglu_stream for
-    17 to 64 rows."""
+    17 to 64 rows.  w8gu, w8d: the fp8 pairs of wgu and wd, as in
+    :func:`project` (ops.gemm.swiglu_skinny_w8)."""
+    if _w8(x, w8gu, True, gemm):
+        return project(_gemm.swiglu_skinny_w8(x, *w8gu, checked=True), wd, gemm, w8d)
     if gemm in ("skinny", "stream"):
         why = _gemm.skinny_refusal(x, wgu, swiglu=True)
         if not why:
-            return project(_gemm.swiglu_skinny(x, wgu), wd, gemm)
+            return project(_gemm.swiglu_skinny(x, wgu), wd, gemm, w8d)
         if gemm == "stream":
             why = _gemm.stream_refusal(x, wgu, swiglu=True)
             if not why:
-                return project(_gemm.swiglu_stream(x, wgu), wd, gemm)
+                return project(_gemm.swiglu_stream(x, wgu), wd, gemm, w8d)
         _gemm._fallback("decode", (x.shape[0], wgu.shape[0], x.shape[1]), "tile", why)
     return swiglu_mlp(x, wgu, wd)
 

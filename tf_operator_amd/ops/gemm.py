@@ -645,6 +645,142 @@ def swiglu_stream(x2: torch.Tensor, wgu: torch.Tensor) -> torch.Tensor:
     return s
 
 
+# ---- 1 to 16 rows on fp8 weights (csrc/hip/gemm_w8.hip; what it takes is csrc/hip/gemm_w8_shapes.h's to say).
+# q [N, K] torch.float8_e4m3fn (OCP e4m3: largest finite 448), scale [N] fp32; y = bf16(scale * (x q^T)), fp32 sums.
+E4M3 = torch.float8_e4m3fn
+W8_E_MIN, W8_E_MAX = -100, 100   # gemm_w8_shapes.h E_MIN, E_MAX
+
+
+def w8_exponents(w: torch.Tensor):
+    """(e int32 [N], finite bool [N]) of the rows of w [N, K]: scale = 2^e, e the
+    least integer with amax <= 448 * 2^e, from amax's exponent and mantissa
+    (448 = 1.75 * 2^8; amax = m * 2^E, 0.5 <= m < 1 by frexp: e = E - 9 if
+    m <= 0.875, else E - 8), 0 for a row of zeros, clamped to -100 .. 100.
+    A row with a non-finite element: e = 0, finite False.  Plain torch on any
+    device: the reference the quantiser kernel is held against."""
+    amax = w.float().abs().amax(1)
+    finite = torch.isfinite(amax)
+    m, E = torch.frexp(torch.where(finite, amax, torch.zeros_like(amax)))
+    e = (E - 9 + (m > 0.875).to(E.dtype)).clamp(W8_E_MIN, W8_E_MAX)
+    return torch.where(amax > 0, e, torch.zeros_like(e)).to(torch.int32), finite
+
+
+def _quantize_ref(w):
+    e, finite = w8_exponents(w)
+    q = torch.ldexp(w.float(), -e[:, None]).to(E4M3)
+    scale = torch.where(finite, torch.ldexp(torch.ones_like(e, dtype=torch.float32), e),
+                        torch.full_like(e, float("nan"), dtype=torch.float32))
+    return q, scale
+
+
+def quantize_w8(w: torch.Tensor):
+    """w [N, K] -> (q [N, K] float8_e4m3fn, scale [N] fp32) with w ~ scale q,
+    one power-of-two scale per row (:func:`w8_exponents`): q = e4m3(w 2^-e),
+    round to nearest even; the product is exact and at most 448, so nothing
+    saturates, and scale q is exactly a bf16 value.  A row with a non-finite
+    element gets scale NaN: that column of y is NaN, as it would be in bf16.
+    On the GPU: toa_quant_w8 (bf16 rows with unit column stride, K a multiple
+    of 16, 16-byte aligned rows; anything else raises ValueError before a
+    launch).  CPU tensors take the formula in plain torch."""
+    if w.dim() != 2 or w.stride(1) != 1 or not w.is_floating_point():
+        raise ValueError(f"quantize_w8: w {tuple(w.shape)} with strides {w.stride()} is not a float matrix with unit "
+                         "column stride")
+    if not _lib.use_hip(w):
+        return _quantize_ref(w)
+    if w.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_w8: dtype {w.dtype}, not bf16")
+    N, K = w.shape
+    q = torch.empty(N, K, device=w.device, dtype=E4M3)
+    scale = torch.empty(N, device=w.device, dtype=torch.float32)
+    rc = _lib.call_ret("toa_quant_w8", _lib.ptr(w), w.stride(0), _lib.ptr(q), K, _lib.ptr(scale), N, K, _lib.stream(w))
+    if rc == HIP_ERROR_INVALID_VALUE:
+        raise ValueError(f"quantize_w8: toa_quant_w8 takes K a positive multiple of 16 and 16-byte aligned rows, not "
+                         f"w {tuple(w.shape)} with row stride {w.stride(0)} at {w.data_ptr():#x}")
+    if rc:
+        raise RuntimeError(f"toa_quant_w8 failed with hipError {rc}")
+    return q, scale
+
+
+def dequantize_w8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] = scale q; exact for a power-of-two scale inside bf16's range (the quantiser's)."""
+    return (q.float() * scale[:, None]).to(torch.bfloat16)
+
+
+def skinny_w8_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_skinny_w8_why")(reason).decode()
+
+
+def skinny_w8_refusal(x2, q, scale, swiglu: bool = False) -> str:
+    """Why (x2 [M, K], q [N, K] float8_e4m3fn, scale [N] fp32) are no operands
+    of the 1-to-16-row GEMM on fp8 weights, "" if they are: matrices with unit
+    column stride and a common K on one device, x2 bf16 on the GPU (any float
+    dtype on the CPU, which takes the fp32 reference), one contiguous fp32
+    scale per row of q, and a shape the launcher's check takes, in its own
+    words."""
+    if not _lib.has("toa_gemm_skinny_w8_check"):
+        return "library built without toa_gemm_skinny_w8"
+    for t in (x2, q):
+        if t.dim() != 2:
+            return f"a {t.dim()}-D tensor, not a matrix"
+        if t.stride(1) != 1:
+            return f"column stride {t.stride(1)}, not 1"
+    if q.dtype != E4M3:
+        return f"q of dtype {q.dtype}, not {E4M3}"
+    if x2.is_cuda and x2.dtype != torch.bfloat16:
+        return f"dtype {x2.dtype}, not bf16"
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != q.shape[0] or not scale.is_contiguous():
+        return f"scale {scale.dtype} {tuple(scale.shape)}, not one contiguous fp32 entry for each of q's {q.shape[0]} rows"
+    if not x2.device == q.device == scale.device:
+        return f"x ({x2.device}), q ({q.device}) and scale ({scale.device}) differ"
+    if q.shape[1] != x2.shape[1]:
+        return f"K={x2.shape[1]} columns against {q.shape[1]} in the weight"
+    M, K = x2.shape
+    N = q.shape[0] // 2 if swiglu else q.shape[0]
+    # y and the workspace are the wrappers' own (contiguous, aligned): x2 stands in for them
+    r = _lib.call_ret("toa_gemm_skinny_w8_check", int(swiglu), x2.data_ptr(), q.data_ptr(), x2.data_ptr(),
+                      x2.data_ptr(), scale.data_ptr(), x2.stride(0), q.stride(0), N, q.shape[0], M, N, K)
+    return f"{skinny_w8_why(r)}: M={M} N={N} K={K}" if r else ""
+
+
+def _skinny_w8_call(name, x2, q, scale, N, swiglu, checked):
+    r = "" if checked else skinny_w8_refusal(x2, q, scale, swiglu)
+    if r:
+        raise ValueError(f"{name}: {r}")
+    if not _lib.use_hip(x2):
+        return None
+    M, K = x2.shape
+    y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
+    nbytes = int(_lib.call_ret(name + "_ws_bytes", N, K))
+    ws = _workspace(x2.device, nbytes) if nbytes > 0 else None
+    _lib.call(name, _lib.ptr(x2), x2.stride(0), _lib.ptr(q), q.stride(0), _lib.ptr(scale), _lib.ptr(y), N, M, N, K,
+              _lib.ptr(ws), _lib.stream(x2))
+    return y
+
+
+def linear_skinny_w8(x2: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """y [M, N] = scale * (x2 [M, K] q [N, K]^T) for M <= 16 on
+    toa_gemm_skinny_w8: q converted to bf16 in registers (exact), fp32
+    accumulation, one fp32 multiply by the scale, one rounding.  Operands
+    skinny_w8_refusal names raise ValueError before a launch (checked: the
+    caller has just asked skinny_w8_refusal itself, ops.decode.project; the
+    launcher still checks what it can see); CPU tensors take the fp32
+    reference."""
+    y = _skinny_w8_call("toa_gemm_skinny_w8", x2, q, scale, q.shape[0], False, checked)
+    return ((x2.float() @ q.float().t()) * scale).to(x2.dtype) if y is None else y
+
+
+def swiglu_skinny_w8(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """s [M, F] = silu(g) * u, (g | u) = scale * (x2 qgu^T), qgu = gate | up
+    [2F, K], for M <= 16 on toa_gemm_skinny_w8_swiglu: both accumulators are
+    scaled in fp32, the product is rounded once; gu is never stored."""
+    F_ = qgu.shape[0] // 2
+    s = _skinny_w8_call("toa_gemm_skinny_w8_swiglu", x2, qgu, scale, F_, True, checked)
+    if s is None:
+        gu = (x2.float() @ qgu.float().t()) * scale
+        s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
+    return s
+
+
 def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:
     """toa_gemm_shape_check for g [N, K] (+)= dy2 [T, N]^T x2 [T, K] on the
     assembly ("wgrad_asm") or the HIP ("wgrad_hip") kernel.  g stands in for

@@ -12,6 +12,17 @@ from ..ops import sample as _sample
 from ..ops.decode import check_gemm
 
 SAMPLERS = ("torch", "device")   # what picks a token from the logits (docs/kernels.md "Sampling")
+WEIGHTS = ("bf16", "fp8")        # what the blocks' projections read (docs/kernels.md "Decoding on fp8 weights")
+
+
+def check_weights(weights):
+    """weights (None: TOA_DECODE_WEIGHTS, default ``bf16``) as one of WEIGHTS
+    or a snapshot (Llama.quantize_projections), else ValueError."""
+    w = os.environ.get("TOA_DECODE_WEIGHTS", "bf16") if weights is None else weights
+    if isinstance(w, str) and w not in WEIGHTS:
+        raise ValueError(f"{'TOA_DECODE_WEIGHTS' if weights is None else 'weights'}={w!r}: expected one of {WEIGHTS} "
+                         "or a snapshot")
+    return w
 
 
 def check_sampler(sampler) -> str:
@@ -36,7 +47,7 @@ def _pick(logits, temperature, top_k, gen):
 @torch.no_grad()
 def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, top_k=0, eos_id=None, seed=0,
              capacity=None, split_keys=None, gemm=None, prefill_chunk=None, top_p=1.0, min_p=0.0, sampler=None,
-             stream_ids=None):
+             stream_ids=None, weights=None):
     """prompts [B, P] token ids (ragged ones right-padded, lengths: host ints,
     default P each) -> (tokens [B, P + max_new_tokens], lengths int64 [B]):
     row b holds its prompt, then its max_new_tokens new tokens from position
@@ -54,6 +65,12 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     prefill_chunk: Llama.prefill's chunk (None: the whole prompt at once
     through the training ops; n >= 1: n tokens at a time through the
     cache-extend kernels).
+    weights: ``bf16``, ``fp8`` or a snapshot from Llama.quantize_projections
+    (None: TOA_DECODE_WEIGHTS, default ``bf16``).  ``fp8`` quantises the
+    blocks' projections once at the start of this call -- so a trainer samples
+    from its current weights -- and the decode steps of up to 16 rows read one
+    byte per weight (Llama.decode_step weights=); it needs gemm ``skinny`` or
+    ``stream``.
 
     sampler (None: TOA_SAMPLER, default ``torch``): ``torch`` is the path
     above.  ``device`` picks every token with ops.sample.sample_tokens: top_p
@@ -88,6 +105,9 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
             raise ValueError(f"temperature {temperature} and top_k {top_k} must not be negative")
         greedy = temperature == 0.0 or top_k == 1
     gemm = check_gemm(gemm)
+    weights = check_weights(weights)
+    if weights == "fp8" and gemm == "tile":
+        raise ValueError('weights="fp8" needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
     lengths = [P] * B if lengths is None else [int(n) for n in lengths]
     if len(lengths) != B or min(lengths) < 1 or max(lengths) > P:
         raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {B}")
@@ -102,6 +122,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     if sampler == "torch" and not greedy:
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
+    weights = None if weights == "bf16" else model.quantize_projections() if weights == "fp8" else weights
     cache = model.new_cache(B, capacity, device=dev)
     pad = 0 if eos_id is None else int(eos_id)
     out = torch.full((B, P + max_new_tokens), pad, device=dev, dtype=prompts.dtype)
@@ -110,7 +131,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     out[:, :P] = torch.where(cols[None, :P] < at[:, None], prompts, out[:, :P])
     rows = torch.arange(B, device=dev)
     done = torch.zeros(B, device=dev, dtype=torch.bool)
-    logits = model.prefill(prompts, cache, lengths, gemm=gemm, chunk=prefill_chunk)
+    logits = model.prefill(prompts, cache, lengths, gemm=gemm, chunk=prefill_chunk, weights=weights)
     for t in range(max_new_tokens):
         if sampler == "torch":
             tok = _pick(logits, temperature, top_k, gen).to(prompts.dtype)
@@ -124,5 +145,5 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
             done = done | (tok == pad)
         out[rows, at + t] = tok
         if t + 1 < max_new_tokens:
-            logits = model.decode_step(tok, cache, split_keys=split_keys, gemm=gemm)
+            logits = model.decode_step(tok, cache, split_keys=split_keys, gemm=gemm, weights=weights)
     return out, at + max_new_tokens

@@ -55,33 +55,7 @@ extern "C" int toa_decode_rope_append(const bf16_t* qkv, const float* cosv, cons
 // loaded.  A maximum of -inf (no key seen yet) is replaced by 0 before it is
 // subtracted, as in lse_merge and the cross-entropy forward.
 // ---------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  const int o = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
-  return v + __int_as_float(o);
-}
-
-// Sum over the LPK (8 or 16) adjacent lanes of a key group, left in every one of them.
-template <int LPK>
-__device__ __forceinline__ float group_sum(float v) {
-  v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-  v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-  v = dpp_add<0x141>(v);  // row_half_mirror: the other quad of the 8
-  if (LPK == 16) v = dpp_add<0x140>(v);  // row_mirror: the other half of the 16
-  return v;
-}
-
-// (m, l, acc) <- (m, l, acc) (+) (m2, l2, acc2), the -inf maximum guarded
-__device__ __forceinline__ void part_merge(float& m, float& l, float* acc, float m2, float l2, const float* acc2) {
-  const float mn = fmaxf(m, m2);
-  const float mr = mn == -INFINITY ? 0.f : mn;
-  const float a1 = exp2_fast(m - mr), a2 = exp2_fast(m2 - mr);
-  l = l * a1 + l2 * a2;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = acc[j] * a1 + acc2[j] * a2;
-  m = mn;
-}
-
+// (group_sum and part_merge: kv_cache.h, shared with the fp8 cache's kernel, kv_cache_q8.hip)
 #define TOA_DECODE_KU 4
 
 template <int D, int GT>

@@ -35,6 +35,8 @@
 // exact no-ops, and a merge over the splits at or below pos, in order.
 #include "kv_cache.h"
 
+#include "kv_cache_q8_shapes.h"
+
 typedef __attribute__((ext_vector_type(8))) short ext_s16x8;
 typedef __attribute__((ext_vector_type(4))) short ext_s16x4;
 
@@ -87,9 +89,29 @@ __device__ __forceinline__ ext_s16x4 ext_tr_read(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
-                                                          const bf16_t* __restrict__ vc, const int* __restrict__ start,
+// Q8: the cache is the fp8 one (kv_cache_q8_shapes.h): kc / vc are e4m3 bytes, ksc / vsc their scales
+// [B, Hkv, C].  Only the staging differs: a thread fetches 8 bytes and the key's scale per chunk instead of 16
+// bytes, and writes byte * scale -- exactly a bf16 value -- into the same LDS image.  Everything after it is shared.
+typedef __attribute__((ext_vector_type(2))) uint32_t ext_u32x2;
+typedef __attribute__((ext_vector_type(2))) float ext_f32x2;
+
+// eight e4m3 bytes times a power-of-two scale -> eight bf16, exact
+__device__ __forceinline__ u32x4 ext_dequant8(ext_u32x2 w, float scale) {
+  u32x4 out;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const ext_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+    const ext_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    out[2 * i] = pack2(lo[0] * scale, lo[1] * scale);
+    out[2 * i + 1] = pack2(hi[0] * scale, hi[1] * scale);
+  }
+  return out;
+}
+
+template <int D, bool Q8>
+__global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restrict__ q, const void* __restrict__ kcv,
+                                                          const void* __restrict__ vcv, const float* __restrict__ ksc,
+                                                          const float* __restrict__ vsc, const int* __restrict__ start,
                                                           const int* __restrict__ count, float* __restrict__ ws_o,
                                                           float* __restrict__ ws_ml, int T, int Hq, int Hkv, int C,
                                                           int max_len, int split, int nsplit, int nchunk,
@@ -136,18 +158,30 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restri
   // rows of K / V that hold this row's keys: below start + count, the cache and max_len
   const int kvalid = min(min(st + cnt, C), max_len);
   const int kend = min(min(k0 + split, wg_lim + 1), kvalid);
-  const bf16_t* kb = kc + ((int64_t)b * Hkv + kvh) * C * D;
-  const bf16_t* vb = vc + ((int64_t)b * Hkv + kvh) * C * D;
+  const int64_t head = ((int64_t)b * Hkv + kvh) * C;
+  const bf16_t* kb = (const bf16_t*)kcv + head * D;  // the bf16 cache's rows
+  const bf16_t* vb = (const bf16_t*)vcv + head * D;
+  const uint8_t* kb8 = (const uint8_t*)kcv + head * D;  // the fp8 cache's
+  const uint8_t* vb8 = (const uint8_t*)vcv + head * D;
 
-  u32x4 stk[NL], stv[NL];
+  u32x4 stk[Q8 ? 1 : NL], stv[Q8 ? 1 : NL];
+  ext_u32x2 stk8[Q8 ? NL : 1], stv8[Q8 ? NL : 1];
+  float stks[Q8 ? NL : 1], stvs[Q8 ? NL : 1];
   auto gload = [&](int base) {
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int e = tid + 256 * i;
-      const int key = base + e / NCH, c = e % NCH;
-      const int64_t off = (int64_t)min(key, kvalid - 1) * D + c * 8;  // clamped: always inside the row's keys
-      stk[i] = ld16(kb + off);
-      stv[i] = ld16(vb + off);
+      const int key = min(base + e / NCH, kvalid - 1), c = e % NCH;  // clamped: always inside the row's keys
+      const int64_t off = (int64_t)key * D + c * 8;
+      if constexpr (Q8) {
+        stk8[i] = *(const ext_u32x2*)(kb8 + off);
+        stv8[i] = *(const ext_u32x2*)(vb8 + off);
+        stks[i] = ksc[head + key];
+        stvs[i] = vsc[head + key];
+      } else {
+        stk[i] = ld16(kb + off);
+        stv[i] = ld16(vb + off);
+      }
     }
   };
   auto swrite = [&](int base) {
@@ -157,8 +191,13 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restri
       const int kr = e / NCH, c = e % NCH;
       const bool in = base + kr < kvalid;
       const u32x4 z = {0u, 0u, 0u, 0u};
-      *(u32x4*)(ks + kr * RS + c * 16) = in ? stk[i] : z;
-      *(u32x4*)(vs + kr * RS + c * 16) = in ? stv[i] : z;
+      if constexpr (Q8) {
+        *(u32x4*)(ks + kr * RS + c * 16) = in ? ext_dequant8(stk8[i], stks[i]) : z;
+        *(u32x4*)(vs + kr * RS + c * 16) = in ? ext_dequant8(stv8[i], stvs[i]) : z;
+      } else {
+        *(u32x4*)(ks + kr * RS + c * 16) = in ? stk[i] : z;
+        *(u32x4*)(vs + kr * RS + c * 16) = in ? stv[i] : z;
+      }
     }
   };
 
@@ -253,9 +292,10 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restri
 // ceil(max_len / split_keys), or 1 for split_keys 0 (one split over all keys).
 // max_len: a host-side bound of start + count (1 .. C) that sizes the grid;
 // keys at or beyond it are not attended.  split_keys: 0 or a power of two >= 64.
-extern "C" int toa_attn_extend(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int* start,
-                               const int* count, float* ws, bf16_t* o, int B, int T, int Hq, int Hkv, int C, int D,
-                               int max_len, int split_keys, float scale, hipStream_t stream) {
+template <bool Q8>
+static int extend_launch(const bf16_t* q, const void* kc, const void* vc, const float* ksc, const float* vsc,
+                         const int* start, const int* count, float* ws, bf16_t* o, int B, int T, int Hq, int Hkv,
+                         int C, int D, int max_len, int split_keys, float scale, hipStream_t stream) {
   if ((D != 64 && D != 128) || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return (int)hipErrorInvalidValue;
   if (split_keys != 0 && (split_keys < 64 || (split_keys & (split_keys - 1)) != 0)) return (int)hipErrorInvalidValue;
   if (B <= 0 || B > 65535 || T < 1 || C <= 0 || max_len < 1 || max_len > C) return (int)hipErrorInvalidValue;
@@ -273,12 +313,32 @@ extern "C" int toa_attn_extend(const bf16_t* q, const bf16_t* kc, const bf16_t* 
   const float scale_log2 = scale * 1.4426950408889634f;
   const dim3 grid(nsplit, (unsigned)gy, B);
   if (D == 128)
-    hipLaunchKernelGGL((attn_extend_kernel<128>), grid, dim3(256), 0, stream, q, kc, vc, start, count, ws_o, ws_ml, T,
-                       Hq, Hkv, C, max_len, split, nsplit, (int)nchunk, scale_log2);
+    hipLaunchKernelGGL((attn_extend_kernel<128, Q8>), grid, dim3(256), 0, stream, q, kc, vc, ksc, vsc, start, count,
+                       ws_o, ws_ml, T, Hq, Hkv, C, max_len, split, nsplit, (int)nchunk, scale_log2);
   else
-    hipLaunchKernelGGL((attn_extend_kernel<64>), grid, dim3(256), 0, stream, q, kc, vc, start, count, ws_o, ws_ml, T,
-                       Hq, Hkv, C, max_len, split, nsplit, (int)nchunk, scale_log2);
+    hipLaunchKernelGGL((attn_extend_kernel<64, Q8>), grid, dim3(256), 0, stream, q, kc, vc, ksc, vsc, start, count,
+                       ws_o, ws_ml, T, Hq, Hkv, C, max_len, split, nsplit, (int)nchunk, scale_log2);
   int rc = (int)hipGetLastError();
   if (rc != 0) return rc;
   return kv_launch_split_merge(ws_o, ws_ml, start, count, o, B, T, Hq, D, C, max_len, split, nsplit, stream);
+}
+
+extern "C" int toa_attn_extend(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int* start,
+                               const int* count, float* ws, bf16_t* o, int B, int T, int Hq, int Hkv, int C, int D,
+                               int max_len, int split_keys, float scale, hipStream_t stream) {
+  return extend_launch<false>(q, kc, vc, nullptr, nullptr, start, count, ws, o, B, T, Hq, Hkv, C, D, max_len,
+                              split_keys, scale, stream);
+}
+
+// The same on the fp8 cache: k8 / v8 [B, Hkv, C, D] e4m3 bytes, kscale / vscale [B, Hkv, C] fp32.
+extern "C" int toa_attn_extend_q8(const bf16_t* q, const uint8_t* k8, const uint8_t* v8, const float* kscale,
+                                  const float* vscale, const int* start, const int* count, float* ws, bf16_t* o,
+                                  int B, int T, int Hq, int Hkv, int C, int D, int max_len, int split_keys,
+                                  float scale, hipStream_t stream) {
+  toa_kvq8::Operands c = {};
+  c.K8 = (uintptr_t)k8, c.V8 = (uintptr_t)v8, c.KSCALE = (uintptr_t)kscale, c.VSCALE = (uintptr_t)vscale;
+  c.B = B, c.T = T, c.Hq = Hq, c.Hkv = Hkv, c.D = D, c.C = C, c.limit = max_len, c.split_keys = split_keys;
+  if (toa_kvq8::check(toa_kvq8::OP_EXTEND, c) != toa_kvq8::R_OK) return (int)hipErrorInvalidValue;
+  return extend_launch<true>(q, k8, v8, kscale, vscale, start, count, ws, o, B, T, Hq, Hkv, C, D, max_len, split_keys,
+                             scale, stream);
 }

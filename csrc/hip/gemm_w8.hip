@@ -236,30 +236,7 @@ int launch(const bf16_t* x, int64_t ldx, const uint8_t* q, int64_t ldw, const fl
   return (int)hipGetLastError();
 }
 
-// ---- the quantiser
-// four floats -> four e4m3 bytes, round to nearest even.  Beyond the format (|f| > 448: only where the exponent met
-// its clamp, or in a row with a non-finite element) the bytes are set here and not left to the conversion's mode:
-// up to the tie at 464 the largest finite code 0x7e, past it and for NaN the NaN code 0x7f, the sign kept.
-__device__ __forceinline__ uint32_t to_e4m3x4(const float* f) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
-  uint32_t out = (uint32_t)w;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (!(fabsf(f[i]) <= 448.f)) {
-      const uint32_t code = (fabsf(f[i]) <= 464.f ? 0x7eu : 0x7fu) | ((__float_as_uint(f[i]) >> 24) & 0x80u);
-      out = (out & ~(0xffu << (8 * i))) | (code << (8 * i));
-    }
-  }
-  return out;
-}
-
-__device__ __forceinline__ uint32_t amax_bits(uint32_t m, const u32x4 v) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) m = max(m, max(v[i] & 0x7fffu, (v[i] >> 16) & 0x7fffu));
-  return m;
-}
-
+// ---- the quantiser (the exponent rule, to_e4m3x4 and amax_bits: e4m3_quant.h)
 __global__ __launch_bounds__(QUANT_BLOCK) void quant_w8_kernel(const bf16_t* __restrict__ w, int64_t ldw,
                                                                uint8_t* __restrict__ q, int64_t ldq,
                                                                float* __restrict__ scale, int K) {

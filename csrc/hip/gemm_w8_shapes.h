@@ -30,6 +30,8 @@
 
 #include <cstdint>
 
+#include "e4m3_quant.h"
+
 namespace toa_w8 {
 
 // ---- the kernel's constants
@@ -130,16 +132,10 @@ constexpr Reason check(int form, const Operands& o) {
 }
 
 // ---- the quantiser: w [N][K] bf16 with row stride ldw elements, q with row stride ldq bytes
-// The exponent e of scale = 2^e from the magnitude bits (sign cleared) of a row's largest |w|, a finite bf16: the
-// least e with amax <= 448 * 2^e = 1.75 * 2^(e + 8), clamped to -100 .. 100; 0 for a row of zeros.  With amax =
-// m * 2^E, 1 <= m < 2: e = E - 8 if m <= 1.75 (mantissa field <= 0x60), else E - 7.  A subnormal amax has E = -127
-// here and meets the clamp either way.
-constexpr int E_MIN = -100, E_MAX = 100;
-constexpr int scale_exponent(uint32_t amax_bits) {
-  if (amax_bits == 0) return 0;
-  const int e = (int)(amax_bits >> 7) - 127 - 8 + ((amax_bits & 0x7f) > 0x60 ? 1 : 0);
-  return e < E_MIN ? E_MIN : e > E_MAX ? E_MAX : e;
-}
+// The exponent e of scale = 2^e of a row: e4m3_quant.h, the rule the fp8 KV cache shares.
+using toa_e4m3::E_MAX;
+using toa_e4m3::E_MIN;
+using toa_e4m3::scale_exponent;
 
 constexpr bool quant_ok(uintptr_t w, uintptr_t q, uintptr_t scale, int64_t ldw, int64_t ldq, int N, int K) {
   return N > 0 && K > 0 && K % CHUNK == 0 && ld_ok(ldw, K, 8) && ld_ok(ldq, K, 16) && al16(w) && al16(q) &&

@@ -50,6 +50,7 @@ def main(argv=None):
     ap.add_argument("--head-dim", type=int, default=128)
     ap.add_argument("--len", type=int, default=4096, dest="length")
     ap.add_argument("--split-keys", type=int, nargs="*", default=None, help="default: ops.decode.SPLIT_KEYS_DEFAULT")
+    ap.add_argument("--fp8", action="store_true", help="also time toa_attn_decode_q8 on the fp8 cache of the same keys")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--iters", type=int, default=50)
     a = ap.parse_args(argv)
@@ -84,6 +85,24 @@ def main(argv=None):
     # the copy again after the kernel runs: the spread between the two copy figures is the noise of this run
     med, lo, hi = _median_ms(lambda: dst.copy_(src), 2, a.iters)
     res["copy_again"] = {"median_us": round(med * 1e3, 2), "read_GBps": round(nbytes / med / 1e6, 1)}
+    if a.fp8:
+        # the fp8 cache of the same keys (toa_attn_decode_q8): its own bytes -- D + 4 per row instead of 2 D -- against
+        # a copy of that many, and against the bf16 kernel above
+        cache = decode.KVCache(1, B, Hkv, L, D, dev, dtype=torch.float8_e4m3fn)
+        k8, v8, ks, vs = cache.k[0], cache.v[0], cache.k_scale[0], cache.v_scale[0]
+        decode.fill_cache(kc, vc, k8, v8, ks, vs)
+        n8 = cache.nbytes()
+        res["kv_bytes_fp8"] = n8
+        med, lo, hi = _median_ms(lambda: dst[:n8].copy_(src[:n8]), a.warmup, a.iters)
+        res["copy_fp8"] = {"median_us": round(med * 1e3, 2), "read_GBps": round(n8 / med / 1e6, 1)}
+        res["attn_decode_q8"] = {}
+        for split in (a.split_keys or [decode.SPLIT_KEYS_DEFAULT]):
+            med, lo, hi = _median_ms(lambda: decode.attn_decode(q, k8, v8, n, split_keys=split, max_len=L, k_scale=ks,
+                                                                v_scale=vs), a.warmup, a.iters)
+            res["attn_decode_q8"][str(split)] = {
+                "median_us": round(med * 1e3, 2), "min_us": round(lo * 1e3, 2), "max_us": round(hi * 1e3, 2),
+                "read_GBps": round(n8 / med / 1e6, 1), "of_copy": round(res["copy_fp8"]["median_us"] / (med * 1e3), 3),
+                "bf16_over_fp8": round(res["attn_decode"][str(split)]["median_us"] / (med * 1e3), 3)}
     print(json.dumps(res))
 
 

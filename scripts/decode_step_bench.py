@@ -283,6 +283,49 @@ def bench_fp8(a, dev):
     return out
 
 
+def bench_kv(a, dev):
+    """The whole decode step on llama3-8b, ``skinny`` projections, B = 1 and 8 at cache length --len: the bf16 cache
+    against the fp8 cache (csrc/hip/kv_cache_q8.hip), ABBA as in bench_step; ms per step and the caches' bytes."""
+    from tf_operator_amd.models.llama import PRESETS, Llama
+
+    m = Llama(PRESETS["llama3-8b"], device=dev)
+    m.init_weights(0)
+    m.eval()
+    out = {"preset": "llama3-8b", "length": a.length, "steps_per_visit": STEPS, "rounds": a.rounds}
+    for B in (1, 8):
+        caches = {"bf16": m.new_cache(B, a.length + STEPS), "fp8": m.new_cache(B, a.length + STEPS,
+                                                                                 dtype=torch.float8_e4m3fn)}
+        tokens = torch.randint(0, m.cfg.vocab_size, (B,), device=dev)
+
+        def visit(kv):
+            cache = caches[kv]
+            cache.set_lengths([a.length] * B)
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(STEPS):
+                m.decode_step(tokens, cache, gemm="skinny")
+            e.record()
+            e.synchronize()
+            return s.elapsed_time(e) / STEPS
+
+        for kv in ("bf16", "fp8"):
+            visit(kv)   # warm-up: code objects, workspaces, allocator
+        t, f, d = [], [], []
+        for _ in range(a.rounds):
+            r = [visit(kv) for kv in ("bf16", "fp8", "fp8", "bf16")]
+            t.append((r[0] + r[3]) / 2)
+            f.append((r[1] + r[2]) / 2)
+            d.append(t[-1] - f[-1])
+        se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
+        out[f"B{B}"] = {"bf16_ms_per_step": round(statistics.mean(t), 4), "fp8_ms_per_step": round(statistics.mean(f), 4),
+                        "bf16_minus_fp8_ms": round(statistics.mean(d), 4), "stderr_ms": round(se, 4),
+                        "cache_bytes": {k: c.nbytes() for k, c in caches.items()}}
+        del caches
+        torch.cuda.empty_cache()
+    return out
+
+
 def bench_extend(a, dev):
     """Llama.extend of T = 4 tokens on B = 8 rows at cache length --len, logits="last": ``tile`` and ``stream``
     alternated ABBA, device events around each call; ms per call."""
@@ -332,6 +375,7 @@ def main(argv=None):
     ap.add_argument("--extend", action="store_true", help="the whole extend call, tile against stream")
     ap.add_argument("--fp8", action="store_true",
                     help="only the fp8 arm beside skinny: per form, the whole step (unless --skip-step), the quantiser")
+    ap.add_argument("--kv", action="store_true", help="only the whole step on the bf16 cache against the fp8 cache")
     a = ap.parse_args(argv)
     if a.iters < 50 or a.rounds < 8:
         ap.error("--iters must be at least 50 and --rounds at least 8")
@@ -345,9 +389,11 @@ def main(argv=None):
     res = {"device": torch.cuda.get_device_name(dev), "gemm_mode": gemm.mode(), "iters": a.iters, "inner": INNER}
     if a.fp8:
         res["fp8"] = bench_fp8(a, dev)
-    if not a.skip_forms and not a.fp8:
+    if a.kv:
+        res["kv"] = bench_kv(a, dev)
+    if not a.skip_forms and not a.fp8 and not a.kv:
         res["forms"] = bench_forms(a, dev)
-    if not a.skip_step and not a.fp8:
+    if not a.skip_step and not a.fp8 and not a.kv:
         res["step"] = bench_step(a, dev)
     if a.extend:
         res["extend"] = bench_extend(a, dev)

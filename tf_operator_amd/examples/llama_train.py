@@ -63,6 +63,9 @@ def main(argv=None):
     p.add_argument("--sample-weights", choices=["bf16", "fp8"], default=None,
                    help="what a sample's projections read: the bf16 weights, or an e4m3 copy quantised at the start of "
                         "each sample (needs --sample-gemm skinny or stream); default: TOA_DECODE_WEIGHTS, else bf16")
+    p.add_argument("--sample-kv", choices=["bf16", "fp8"], default=None,
+                   help="a sample's KV cache: bf16, or e4m3 keys and values with one scale per token and KV head (half "
+                        "the bytes); default: TOA_DECODE_KV, else bf16")
     p.add_argument("--sample-prefill-chunk", type=int, default=None, metavar="N",
                    help="prefill a sample's prompt N tokens at a time through the cache-extend kernels instead of all "
                         "at once through the training ops; default: all at once")
@@ -132,7 +135,7 @@ def _sample(a, tr, tokens):
     P = a.sample_prompt_len
     out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm, prefill_chunk=a.sample_prefill_chunk,
                          temperature=a.sample_temperature, top_k=a.sample_top_k, top_p=a.sample_top_p,
-                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler, weights=a.sample_weights)
+                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler, weights=a.sample_weights, kv=a.sample_kv)
     print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
 
 

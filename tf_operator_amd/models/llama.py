@@ -192,7 +192,10 @@ class Llama(torch.nn.Module):
 
     # ---- KV-cache decoding (ops/decode.py; docs/kernels.md "Decoding").  Additions: forward is as it was.
     def new_cache(self, batch, capacity, device=None, dtype=None):
-        """An empty KVCache of this model's layers, KV heads and head dim."""
+        """An empty KVCache of this model's layers, KV heads and head dim.
+        dtype=torch.float8_e4m3fn: the fp8 cache (e4m3 keys and values with one
+        power-of-two scale per token and KV head, half the bytes; docs/kernels.md
+        "fp8 KV cache"); prefill, extend and decode_step take either."""
         w = self.embed.weight
         return KVCache(self.cfg.layers, batch, self.cfg.kv_heads, capacity, self.cfg.head_dim,
                        w.device if device is None else device, w.dtype if dtype is None else dtype)
@@ -305,8 +308,11 @@ class Llama(torch.nn.Module):
 
         def attend(i, qkv):
             q, k, v = rope_qkv(qkv, cos, sin, B, P, Hq, Hkv, D, 1)
-            cache.k[i][:, :, :P] = k
-            cache.v[i][:, :, :P] = v
+            if cache.k_scale is None:
+                cache.k[i][:, :, :P] = k
+                cache.v[i][:, :, :P] = v
+            else:   # the attention below still reads the unquantised k and v
+                _dec.fill_cache(k, v, cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i])
             return causal_attention(q, k, v, out_layout="bshd").reshape(B * P, Hq * D)
 
         h, delta = self._cached_blocks(self.embed(tokens).view(B * P, cfg.hidden), attend, "tile")
@@ -353,8 +359,10 @@ class Llama(torch.nn.Module):
         cos, sin, _ = self.rope(cache.capacity, tokens.device)
 
         def attend(i, qkv):
-            q = _dec.rope_append_many(qkv.view(B, T, -1), cos, sin, start, count, cache.k[i], cache.v[i], Hq, Hkv, D)
-            o = _dec.attn_extend(q, cache.k[i], cache.v[i], start, count, split_keys=split_keys, max_len=max_len)
+            sc = cache.scales(i)
+            q = _dec.rope_append_many(qkv.view(B, T, -1), cos, sin, start, count, cache.k[i], cache.v[i], Hq, Hkv, D,
+                                      **sc)
+            o = _dec.attn_extend(q, cache.k[i], cache.v[i], start, count, split_keys=split_keys, max_len=max_len, **sc)
             return o.view(B * T, Hq * D)
 
         h, delta = self._cached_blocks(self.embed(tokens).view(B * T, cfg.hidden), attend, gemm, weights)
@@ -397,8 +405,9 @@ class Llama(torch.nn.Module):
         pos, lens, max_len = cache.positions, cache.lengths, cache.max_len
 
         def attend(i, qkv):
-            q = rope_append(qkv, cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D)
-            o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len)
+            sc = cache.scales(i)
+            q = rope_append(qkv, cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D, **sc)
+            o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len, **sc)
             return o.view(B, Hq * D)
 
         h, delta = self._cached_blocks(self.embed(tokens), attend, gemm, weights)

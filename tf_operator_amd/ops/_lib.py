@@ -119,6 +119,15 @@ _SIGS = {
                                c_int, c_p],
     "toa_attn_extend": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                         c_f, c_p],
+    # the fp8 KV cache (csrc/hip/kv_cache_q8.hip, kv_cache_q8_shapes.h; the extend kernel is extend.hip's): the bf16
+    # launchers' arguments with k8 v8 k_scale v_scale in the two caches' place.  The fill: k v, the cache's four,
+    # B Hkv P D C.  The check: op, the cache's four, B T Hq Hkv D C limit split_keys
+    "toa_decode_rope_append_q8": [c_p] * 9 + [c_int] * 6 + [c_p],
+    "toa_extend_rope_append_q8": [c_p] * 10 + [c_int] * 7 + [c_p],
+    "toa_kv_quant_rows": [c_p] * 6 + [c_int] * 5 + [c_p],
+    "toa_attn_decode_q8": [c_p] * 8 + [c_int] * 7 + [c_f, c_p],
+    "toa_attn_extend_q8": [c_p] * 9 + [c_int] * 8 + [c_f, c_p],
+    "toa_kv_q8_check": [c_int] + [c_p] * 4 + [c_int] * 8,
     # sampling (csrc/hip/sample.hip): dtype logits ld, B V, temperature top_k top_p min_p stream_id position (per
     # row), seed, tokens, weights (or null), stream
     "toa_sample_tokens": [c_int, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_uint32, c_p, c_p,
@@ -248,7 +257,7 @@ def _load():
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
-        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why"):
+        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_kv_q8_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -281,7 +290,7 @@ _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coher
                     "toa_wgrad_asm_workspace", "toa_gemm_shape_why", "toa_gemm_skinny_ws_bytes",
                     "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why", "toa_gemm_stream_ws_bytes",
                     "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why", "toa_gemm_skinny_w8_ws_bytes",
-                    "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why"}
+                    "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why", "toa_kv_q8_why"}
 
 
 def _fn(name: str):

@@ -27,6 +27,7 @@ from .linear import linear
 from .llm import swiglu_mlp
 
 HEAD_DIMS = (64, 128)     # the kernels' head-dim instantiations (csrc/hip/decode.hip)
+E4M3 = torch.float8_e4m3fn   # the fp8 KV cache's bytes (csrc/hip/kv_cache_q8.hip; docs/kernels.md "fp8 KV cache")
 # keys per workgroup of toa_attn_decode.  Chosen for long caches: 4096 keys x 8 KV heads x 8 rows are 1024
 # workgroups (4 per CU) of 128 KB of K + V each at head_dim 128
 SPLIT_KEYS_DEFAULT = 256
@@ -138,11 +139,18 @@ class KVCache:
                              f"capacity {capacity})")
         if head_dim not in HEAD_DIMS:
             raise ValueError(f"head_dim {head_dim} not in {HEAD_DIMS}")
+        if not (dtype.is_floating_point and (dtype.itemsize > 1 or dtype == E4M3)):
+            raise ValueError(f"KVCache dtype {dtype}: a float type of 2 bytes or more, or {E4M3}")
         self.layers, self.batch, self.kv_heads, self.capacity, self.head_dim = layers, batch, kv_heads, capacity, head_dim
         self.device, self.dtype = torch.device(device), dtype
         shape = (batch, kv_heads, capacity, head_dim)
         self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(layers)]
         self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(layers)]
+        # the fp8 cache: one power-of-two scale per (row, kv head, slot) beside the e4m3 bytes; None otherwise
+        self.k_scale = self.v_scale = None
+        if dtype == E4M3:
+            self.k_scale = [torch.ones(shape[:3], device=device, dtype=torch.float32) for _ in range(layers)]
+            self.v_scale = [torch.ones(shape[:3], device=device, dtype=torch.float32) for _ in range(layers)]
         self.host_lengths = [0] * batch
         # row 0: the last filled slot of each row (the position the newest token was appended at),
         # row 1: the lengths.  One tensor, so one in-place add advances both.
@@ -162,6 +170,17 @@ class KVCache:
     @property
     def max_len(self) -> int:
         return max(self.host_lengths)
+
+    def scales(self, layer) -> dict:
+        """The k_scale= / v_scale= arguments of the ops for this layer: the fp8 cache's scales, else None."""
+        if self.k_scale is None:
+            return dict(k_scale=None, v_scale=None)
+        return dict(k_scale=self.k_scale[layer], v_scale=self.v_scale[layer])
+
+    def nbytes(self) -> int:
+        """Bytes of the cache's tensors, the scales included."""
+        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in ts)
 
     def set_lengths(self, lengths):
         """The rows' lengths after a prefill (host ints); raises before anything is written."""
@@ -206,14 +225,57 @@ class KVCache:
         return sc[0], sc[1]
 
 
-def _check_cache(k_cache, v_cache, B, Hkv, D, like):
+def _check_cache(k_cache, v_cache, B, Hkv, D, like, k_scale=None, v_scale=None):
+    """The caches against the tensor they serve (`like`: qkv or q), and the
+    pair of scales: required exactly when the caches are e4m3, fp32
+    [B, Hkv, C] each.  Returns True for the fp8 cache."""
+    q8 = k_cache.dtype == E4M3
+    want = E4M3 if q8 else like.dtype
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if t.dim() != 4 or t.shape[0] != B or t.shape[1] != Hkv or t.shape[3] != D:
             raise ValueError(f"{name} {tuple(t.shape)} is not [B={B}, Hkv={Hkv}, C, D={D}]")
-        if t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous {like.dtype} on {like.device}")
+        if t.dtype != want or t.device != like.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous {want} on {like.device}")
     if k_cache.shape != v_cache.shape:
         raise ValueError(f"k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} differ")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if not q8:
+            if t is not None:
+                raise ValueError(f"{name} given with {k_cache.dtype} caches: the scales belong to {E4M3} caches")
+        elif t is None:
+            raise ValueError(f"{E4M3} caches need k_scale and v_scale, fp32 {tuple(k_cache.shape[:3])}")
+        elif (t.dtype != torch.float32 or t.shape != k_cache.shape[:3] or t.device != like.device
+              or not t.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous fp32 {tuple(k_cache.shape[:3])} on {like.device} (got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device})")
+    return q8
+
+
+Q8_OPS = ("append", "fill", "decode", "extend")   # kv_cache_q8_shapes.h's enum Op, in its order
+
+
+def _q8_call(name, args, op, k_cache, v_cache, k_scale, v_scale, B, T, Hq, Hkv, D, limit, split_keys=0):
+    """Launcher `name` of the fp8 cache.  It refuses operands its check (kv_cache_q8_shapes.h) does not take before
+    any launch; the same check, asked through toa_kv_q8_check only then, names the reason: ValueError in its words.
+    A decode step is bound by the host's launches, so nothing is asked beforehand."""
+    rc = _lib.call_ret(name, *args)
+    if rc == _gemm.HIP_ERROR_INVALID_VALUE:
+        r = _lib.call_ret("toa_kv_q8_check", Q8_OPS.index(op), _lib.ptr(k_cache), _lib.ptr(v_cache),
+                          _lib.ptr(k_scale), _lib.ptr(v_scale), B, T, Hq, Hkv, D, k_cache.shape[2], limit, split_keys)
+        raise ValueError(f"{name}: {_lib._fn('toa_kv_q8_why')(r).decode() if r else 'refused'}")
+    if rc:
+        raise RuntimeError(f"{name} failed with hipError {rc}")
+
+
+def _quant_rows(x):
+    """x [..., D] -> (e4m3 [..., D], fp32 [...]): ops.gemm's quantiser formula on every D-wide row."""
+    q, scale = _gemm._quantize_ref(x.reshape(-1, x.shape[-1]))
+    return q.view(x.shape), scale.view(x.shape[:-1])
+
+
+def dequantize_cache(cache, scale, dtype=torch.bfloat16):
+    """scale * e4m3 [B, Hkv, C, D] in `dtype`: exact in bf16 for the quantiser's power-of-two scales."""
+    return (cache.float() * scale[..., None]).to(dtype)
 
 
 def _check_rows(name, t, B, device):
@@ -228,7 +290,7 @@ def _need_bf16(fn, t):
         raise RuntimeError(f"HIP {fn} needs bf16 (got {t.dtype})")
 
 
-def _check_rope(qkv, many, cos, sin, rows, k_cache, v_cache, Hq, Hkv, D):
+def _check_rope(qkv, many, cos, sin, rows, k_cache, v_cache, Hq, Hkv, D, k_scale=None, v_scale=None):
     """The arguments of rope_append (qkv [B, W]) and, many, of rope_append_many
     (qkv [B, T, W]); rows: the int32 [B] tensors by name, returned contiguous."""
     _check_heads(Hq, Hkv, D)
@@ -236,14 +298,14 @@ def _check_rope(qkv, many, cos, sin, rows, k_cache, v_cache, Hq, Hkv, D):
     if qkv.dim() != 2 + many or (many and qkv.shape[1] < 1) or qkv.shape[-1] != width:
         raise ValueError(f"qkv {tuple(qkv.shape)} is not [B,{' T >= 1,' if many else ''} (Hq + 2 Hkv) D = {width}]")
     B = qkv.shape[0]
-    _check_cache(k_cache, v_cache, B, Hkv, D, qkv)
+    _check_cache(k_cache, v_cache, B, Hkv, D, qkv, k_scale, v_scale)
     rows = [_check_rows(name, t, B, qkv.device) for name, t in rows.items()]
     if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.dtype != torch.float32:
         raise ValueError(f"cos / sin {tuple(cos.shape)} {cos.dtype} are not fp32 [rows, D/2 = {D // 2}]")
     return rows
 
 
-def _check_attn(q, many, k_cache, v_cache, rows, max_len, scale):
+def _check_attn(q, many, k_cache, v_cache, rows, max_len, scale, k_scale=None, v_scale=None):
     """The arguments of attn_decode (q [B, Hq, D]) and, many, of attn_extend
     (q [B, T, Hq, D]); rows as in _check_rope.  Returns (rows, max_len, scale)
     with the defaults filled in."""
@@ -254,7 +316,7 @@ def _check_attn(q, many, k_cache, v_cache, rows, max_len, scale):
         raise ValueError(f"k_cache {tuple(k_cache.shape)} is not [B, Hkv, C, D]")
     Hkv, C = k_cache.shape[1], k_cache.shape[2]
     _check_heads(Hq, Hkv, D)
-    _check_cache(k_cache, v_cache, B, Hkv, D, q)
+    _check_cache(k_cache, v_cache, B, Hkv, D, q, k_scale, v_scale)
     rows = [_check_rows(name, t, B, q.device) for name, t in rows.items()]
     max_len = C if max_len is None else int(max_len)
     if not 1 <= max_len <= C:
@@ -262,10 +324,20 @@ def _check_attn(q, many, k_cache, v_cache, rows, max_len, scale):
     return rows, max_len, 1.0 / math.sqrt(D) if scale is None else float(scale)
 
 
-def _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D):
+def _put(cache, scale, b, s, n, rows):
+    """rows [n, Hkv, D] into slots s .. s + n - 1 of row b; quantised where the cache has scales."""
+    rows = rows.transpose(0, 1)
+    if scale is None:
+        cache[b, :, s:s + n] = rows
+    else:
+        cache[b, :, s:s + n], scale[b, :, s:s + n] = _quant_rows(rows)
+
+
+def _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D, k_scale=None, v_scale=None):
     """The CPU reference of both rope-appends, qkv [B, T, W]; count None: T
     each.  A token that is not there (t >= count, a position outside the cache
-    or the table) is skipped: nothing appended, a zero q row."""
+    or the table) is skipped: nothing appended, a zero q row.  With scales the
+    caches are e4m3: the rows the plain cache would hold, quantised."""
     B, T = qkv.shape[:2]
     C = k_cache.shape[2]
     q = torch.zeros(B, T, Hq, D, dtype=qkv.dtype)
@@ -280,8 +352,8 @@ def _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D):
         c, sn = cos[s:s + n, None], sin[s:s + n, None]
         r = torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn], -1).to(qkv.dtype)     # [n, Hq + Hkv, D]
         q[b, :n] = r[:, :Hq]
-        k_cache[b, :, s:s + n] = r[:, Hq:].transpose(0, 1)
-        v_cache[b, :, s:s + n] = xb[:, Hq + Hkv:].transpose(0, 1)
+        _put(k_cache, k_scale, b, s, n, r[:, Hq:])
+        _put(v_cache, v_scale, b, s, n, xb[:, Hq + Hkv:])
     return q
 
 
@@ -305,8 +377,13 @@ def _attn_ref(q, k_cache, v_cache, start, count, max_len, scale):
     return out
 
 
-def rope_append(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv, D):
-    """One token per row: qkv [B, (Hq + 2 Hkv) D] (the fused projection's
+def rope_append(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv, D, k_scale=None, v_scale=None):
+    """k_scale, v_scale: fp32 [B, Hkv, C], required exactly when the caches
+    are float8_e4m3fn (KVCache(dtype=torch.float8_e4m3fn)): the slot then
+    holds the bf16 row quantised by ops.gemm.quantize_w8's rule and its scale
+    (toa_decode_rope_append_q8); q is the same bits either way.
+
+    One token per row: qkv [B, (Hq + 2 Hkv) D] (the fused projection's
     output), cos / sin [rows, D/2] fp32 (ops.llm.rope_tables), pos int32 [B]
     on the device.  Rotates q and k at position pos[b] with the convention
     and the roundings of ops.llm.rope_qkv, returns q [B, Hq, D] and stores k
@@ -314,16 +391,22 @@ def rope_append(qkv, cos, sin, pos, k_cache, v_cache, Hq, Hkv, D):
     written.  Positions are the caller's (KVCache.positions, which never
     leaves the cache): a position outside the cache or the table writes
     nothing to the caches and a zero q row, as in rope_append_many."""
-    (pos,) = _check_rope(qkv, False, cos, sin, {"pos": pos}, k_cache, v_cache, Hq, Hkv, D)
+    (pos,) = _check_rope(qkv, False, cos, sin, {"pos": pos}, k_cache, v_cache, Hq, Hkv, D, k_scale, v_scale)
     B, C = qkv.shape[0], k_cache.shape[2]
     if _lib.use_hip(qkv):
         _need_bf16("rope_append", qkv)
         qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
         q = torch.empty(B, Hq, D, device=qkv.device, dtype=qkv.dtype)
+        if k_scale is not None:
+            _q8_call("toa_decode_rope_append_q8",
+                     (_lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(pos), _lib.ptr(q), _lib.ptr(k_cache),
+                      _lib.ptr(v_cache), _lib.ptr(k_scale), _lib.ptr(v_scale), B, Hq, Hkv, D, C, cos.shape[0],
+                      _lib.stream(qkv)), "append", k_cache, v_cache, k_scale, v_scale, B, 1, Hq, Hkv, D, cos.shape[0])
+            return q
         _lib.call("toa_decode_rope_append", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(pos), _lib.ptr(q),
                   _lib.ptr(k_cache), _lib.ptr(v_cache), B, Hq, Hkv, D, C, cos.shape[0], _lib.stream(qkv))
         return q
-    return _rope_ref(qkv[:, None], cos, sin, pos, None, k_cache, v_cache, Hq, Hkv, D)[:, 0]
+    return _rope_ref(qkv[:, None], cos, sin, pos, None, k_cache, v_cache, Hq, Hkv, D, k_scale, v_scale)[:, 0]
 
 
 def decode_ws_floats(B, Hq, D, max_len, split_keys) -> int:
@@ -332,9 +415,12 @@ def decode_ws_floats(B, Hq, D, max_len, split_keys) -> int:
     return B * Hq * -(-max_len // split_keys) * (D + 2)
 
 
-def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_len=None):
+def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_len=None, k_scale=None, v_scale=None):
     """q [B, Hq, D] against the caches [B, Hkv, C, D]: row b attends keys
     0 .. lengths[b]-1 (int32 [B] on the device); returns O [B, Hq, D].
+    k_scale, v_scale: as in rope_append; on float8_e4m3fn caches the GPU runs
+    toa_attn_decode_q8, which reads half the bytes and computes what the bf16
+    kernel computes on the dequantised cache.
 
     On the GPU: toa_attn_decode, split_keys keys per workgroup (a power of
     two >= 64; None: SPLIT_KEYS_DEFAULT) and a merge kernel.  max_len: a
@@ -342,7 +428,8 @@ def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_l
     sizes the grid -- nothing is read back from the device.  A row's result
     depends on that row's q, cache, length and split_keys only."""
     split = check_split_keys(split_keys)
-    (lengths,), max_len, scale = _check_attn(q, False, k_cache, v_cache, {"lengths": lengths}, max_len, scale)
+    (lengths,), max_len, scale = _check_attn(q, False, k_cache, v_cache, {"lengths": lengths}, max_len, scale,
+                                             k_scale, v_scale)
     B, Hq, D = q.shape
     Hkv, C = k_cache.shape[1], k_cache.shape[2]
     if _lib.use_hip(q):
@@ -350,9 +437,17 @@ def attn_decode(q, k_cache, v_cache, lengths, scale=None, split_keys=None, max_l
         q = q.contiguous()
         ws = torch.empty(decode_ws_floats(B, Hq, D, max_len, split), device=q.device, dtype=torch.float32)
         o = torch.empty_like(q)
+        if k_scale is not None:
+            _q8_call("toa_attn_decode_q8",
+                     (_lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(k_scale), _lib.ptr(v_scale),
+                      _lib.ptr(lengths), _lib.ptr(ws), _lib.ptr(o), B, Hq, Hkv, C, D, max_len, split, scale,
+                      _lib.stream(q)), "decode", k_cache, v_cache, k_scale, v_scale, B, 1, Hq, Hkv, D, max_len, split)
+            return o
         _lib.call("toa_attn_decode", _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(lengths),
                   _lib.ptr(ws), _lib.ptr(o), B, Hq, Hkv, C, D, max_len, split, scale, _lib.stream(q))
         return o
+    if k_scale is not None:
+        k_cache, v_cache = dequantize_cache(k_cache, k_scale, q.dtype), dequantize_cache(v_cache, v_scale, q.dtype)
     # one token per row at the last of its keys, the lengths cut to the cache as the kernel cuts them
     return _attn_ref(q[:, None], k_cache, v_cache, lengths.clamp(max=C) - 1, None, max_len, scale)[:, 0]
 
@@ -386,30 +481,71 @@ def extend_ws_floats(B, T, Hq, D, max_len, split_keys) -> int:
     return B * T * Hq * (-(-max_len // split_keys) if split_keys else 1) * (D + 2)
 
 
-def rope_append_many(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D):
-    """T tokens per row: qkv [B, T, (Hq + 2 Hkv) D], cos / sin [rows, D/2]
+def rope_append_many(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D, k_scale=None, v_scale=None):
+    """k_scale, v_scale: as in rope_append (toa_extend_rope_append_q8).
+
+    T tokens per row: qkv [B, T, (Hq + 2 Hkv) D], cos / sin [rows, D/2]
     fp32, start and count int32 [B] on the device (KVCache.extend).  Token t
     of row b sits at position start[b] + t if t < count[b]: q and k are
     rotated there with rope_append's expressions, k and v stored into that
     slot of the caches [B, Hkv, C, D]; returns q [B, T, Hq, D].  A token with
     t >= count[b], or whose position is outside the cache or the table, writes
     nothing to the caches and a zero q row."""
-    start, count = _check_rope(qkv, True, cos, sin, {"start": start, "count": count}, k_cache, v_cache, Hq, Hkv, D)
+    start, count = _check_rope(qkv, True, cos, sin, {"start": start, "count": count}, k_cache, v_cache, Hq, Hkv, D,
+                               k_scale, v_scale)
     B, T = qkv.shape[:2]
     C = k_cache.shape[2]
     if _lib.use_hip(qkv):
         _need_bf16("rope_append_many", qkv)
         qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
         q = torch.empty(B, T, Hq, D, device=qkv.device, dtype=qkv.dtype)
+        if k_scale is not None:
+            _q8_call("toa_extend_rope_append_q8",
+                     (_lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(start), _lib.ptr(count), _lib.ptr(q),
+                      _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(k_scale), _lib.ptr(v_scale), B, T, Hq, Hkv, D, C,
+                      cos.shape[0], _lib.stream(qkv)), "append", k_cache, v_cache, k_scale, v_scale, B, T, Hq, Hkv, D,
+                     cos.shape[0])
+            return q
         _lib.call("toa_extend_rope_append", _lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(start),
                   _lib.ptr(count), _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), B, T, Hq, Hkv, D, C,
                   cos.shape[0], _lib.stream(qkv))
         return q
-    return _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D)
+    return _rope_ref(qkv, cos, sin, start, count, k_cache, v_cache, Hq, Hkv, D, k_scale, v_scale)
 
 
-def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, max_len=None, workspace=None):
-    """q [B, T, Hq, D] against the caches [B, Hkv, C, D]: query (b, t, h),
+def fill_cache(k, v, k_cache, v_cache, k_scale, v_scale):
+    """A whole prompt's rotated k and v [B, Hkv, P, D] into slots 0 .. P - 1
+    of the fp8 cache [B, Hkv, C, D] and its scales [B, Hkv, C]: every D-wide
+    row quantised as rope_append quantises it.  Slots at or beyond P are not
+    touched.  On the GPU: toa_kv_quant_rows, one row per D / 8 lanes."""
+    if k.dim() != 4 or k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
+        raise ValueError(f"k {tuple(k.shape)} {k.dtype} and v {tuple(v.shape)} {v.dtype} are not one [B, Hkv, P, D]")
+    B, Hkv, P, D = k.shape
+    if D not in HEAD_DIMS:
+        raise ValueError(f"head_dim {D} not in {HEAD_DIMS}")
+    if not _check_cache(k_cache, v_cache, B, Hkv, D, k, k_scale, v_scale):
+        raise ValueError(f"fill_cache fills {E4M3} caches, not {k_cache.dtype} (a plain cache takes a slice assignment)")
+    if not 1 <= P <= k_cache.shape[2]:
+        raise ValueError(f"KV cache overflow: {P} rows for a capacity of {k_cache.shape[2]}")
+    if _lib.use_hip(k):
+        _need_bf16("fill_cache", k)
+        k, v = k.contiguous(), v.contiguous()
+        _q8_call("toa_kv_quant_rows",
+                 (_lib.ptr(k), _lib.ptr(v), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(k_scale), _lib.ptr(v_scale),
+                  B, Hkv, P, D, k_cache.shape[2], _lib.stream(k)), "fill", k_cache, v_cache, k_scale, v_scale, B, P, 0,
+                 Hkv, D, 0)
+        return
+    k_cache[:, :, :P], k_scale[:, :, :P] = _quant_rows(k)
+    v_cache[:, :, :P], v_scale[:, :, :P] = _quant_rows(v)
+
+
+def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, max_len=None, workspace=None,
+                k_scale=None, v_scale=None):
+    """k_scale, v_scale: as in rope_append; on float8_e4m3fn caches the GPU
+    runs toa_attn_extend_q8, the same kernel with a staging that dequantises
+    into the LDS image: bit for bit the result on the dequantised cache.
+
+    q [B, T, Hq, D] against the caches [B, Hkv, C, D]: query (b, t, h),
     t < count[b], attends keys 0 .. start[b] + t of KV head h / (Hq / Hkv) --
     its own key is in the cache already, rope_append_many ran first; returns
     O [B, T, Hq, D], rows of zeros for tokens with t >= count[b].
@@ -424,7 +560,7 @@ def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, 
     and split_keys only -- not on T, its index in the call, count, max_len or
     the batch."""
     (start, count), max_len, scale = _check_attn(q, True, k_cache, v_cache, {"start": start, "count": count}, max_len,
-                                                 scale)
+                                                 scale, k_scale, v_scale)
     B, T, Hq, D = q.shape
     Hkv, C = k_cache.shape[1], k_cache.shape[2]
     split = check_extend_split(extend_split(B, T, Hq, Hkv, max_len) if split_keys is None else split_keys)
@@ -439,8 +575,17 @@ def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, 
         q = q.contiguous()
         ws = torch.empty(words, device=q.device, dtype=torch.float32) if workspace is None else workspace
         o = torch.empty_like(q)
+        if k_scale is not None:
+            _q8_call("toa_attn_extend_q8",
+                     (_lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(k_scale), _lib.ptr(v_scale),
+                      _lib.ptr(start), _lib.ptr(count), _lib.ptr(ws), _lib.ptr(o), B, T, Hq, Hkv, C, D, max_len, split,
+                      scale, _lib.stream(q)), "extend", k_cache, v_cache, k_scale, v_scale, B, T, Hq, Hkv, D, max_len,
+                     split)
+            return o
         _lib.call("toa_attn_extend", _lib.ptr(q), _lib.ptr(k_cache), _lib.ptr(v_cache), _lib.ptr(start),
                   _lib.ptr(count), _lib.ptr(ws), _lib.ptr(o), B, T, Hq, Hkv, C, D, max_len, split, scale,
                   _lib.stream(q))
         return o
+    if k_scale is not None:
+        k_cache, v_cache = dequantize_cache(k_cache, k_scale, q.dtype), dequantize_cache(v_cache, v_scale, q.dtype)
     return _attn_ref(q, k_cache, v_cache, start, count, max_len, scale)

@@ -25,6 +25,17 @@ def check_weights(weights):
     return w
 
 
+KVS = ("bf16", "fp8")            # what the KV cache holds (docs/kernels.md "fp8 KV cache")
+
+
+def check_kv(kv) -> str:
+    """kv (None: TOA_DECODE_KV, default ``bf16``) as one of KVS, else ValueError."""
+    k = os.environ.get("TOA_DECODE_KV", "bf16") if kv is None else kv
+    if k not in KVS:
+        raise ValueError(f"{'TOA_DECODE_KV' if kv is None else 'kv'}={k!r}: expected one of {KVS}")
+    return k
+
+
 def check_sampler(sampler) -> str:
     """sampler (None: TOA_SAMPLER, default ``torch``) as one of SAMPLERS, else ValueError."""
     s = os.environ.get("TOA_SAMPLER", "torch") if sampler is None else sampler
@@ -47,7 +58,7 @@ def _pick(logits, temperature, top_k, gen):
 @torch.no_grad()
 def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, top_k=0, eos_id=None, seed=0,
              capacity=None, split_keys=None, gemm=None, prefill_chunk=None, top_p=1.0, min_p=0.0, sampler=None,
-             stream_ids=None, weights=None):
+             stream_ids=None, weights=None, kv=None):
     """prompts [B, P] token ids (ragged ones right-padded, lengths: host ints,
     default P each) -> (tokens [B, P + max_new_tokens], lengths int64 [B]):
     row b holds its prompt, then its max_new_tokens new tokens from position
@@ -71,6 +82,11 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     from its current weights -- and the decode steps of up to 16 rows read one
     byte per weight (Llama.decode_step weights=); it needs gemm ``skinny`` or
     ``stream``.
+    kv: ``bf16`` or ``fp8`` (None: TOA_DECODE_KV, default ``bf16``): the KV
+    cache in the model's dtype, or e4m3 keys and values with one power-of-two
+    scale per token and KV head (Llama.new_cache(dtype=torch.float8_e4m3fn):
+    half the cache's bytes and half of what a decode step streams from it).
+    Independent of gemm and weights.
 
     sampler (None: TOA_SAMPLER, default ``torch``): ``torch`` is the path
     above.  ``device`` picks every token with ops.sample.sample_tokens: top_p
@@ -106,6 +122,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
         greedy = temperature == 0.0 or top_k == 1
     gemm = check_gemm(gemm)
     weights = check_weights(weights)
+    kv = check_kv(kv)
     if weights == "fp8" and gemm == "tile":
         raise ValueError('weights="fp8" needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
     lengths = [P] * B if lengths is None else [int(n) for n in lengths]
@@ -123,7 +140,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
     weights = None if weights == "bf16" else model.quantize_projections() if weights == "fp8" else weights
-    cache = model.new_cache(B, capacity, device=dev)
+    cache = model.new_cache(B, capacity, device=dev, dtype=torch.float8_e4m3fn if kv == "fp8" else None)
     pad = 0 if eos_id is None else int(eos_id)
     out = torch.full((B, P + max_new_tokens), pad, device=dev, dtype=prompts.dtype)
     cols = torch.arange(P + max_new_tokens, device=dev)

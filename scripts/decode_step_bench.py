@@ -23,8 +23,10 @@ whatever the host's launch cost leaves exposed.
 One JSON line.
 
 ``--fp8``: the 1-to-16-row GEMM on fp8 weights (csrc/hip/gemm_w8.hip) beside
-``skinny``, per form against a copy of q's bytes and as a whole step on a
-snapshot (bench_fp8).
+``skinny`` and the 17-to-64-row one (csrc/hip/gemm_stream_w8.hip) beside
+``stream``, per form against a copy of q's bytes, and as a whole step and a
+whole extend call on a snapshot (bench_fp8).  With ``--only-stream``: the
+17-to-64-row arms and the extend call alone.
 
     python scripts/decode_step_bench.py [--iters 50] [--rounds 8] [--skip-step] [--skip-forms] [--only-stream]
                                         [--extend] [--fp8]
@@ -45,6 +47,7 @@ FORMS = (("qkv", 6144, 4096, False), ("attn_out", 4096, 4096, False), ("gate_up"
          ("down", 4096, 14336, False), ("head", 128256, 4096, False))   # (name, N or F, K, SwiGLU)
 MS = (1, 8, 16)
 STREAM_MS = (17, 32, 48, 64)   # the 17-to-64-row kernel (csrc/hip/gemm_stream.hip): the ``stream`` arm against ``tile``
+STREAM_W8_MS = (17, 32, 64)    # the 17-to-64-row kernel on fp8 weights (csrc/hip/gemm_stream_w8.hip) against ``stream``
 STEPS = 16          # decode steps per arm visit of the whole-step ABBA
 
 
@@ -195,7 +198,9 @@ def bench_fp8(a, dev):
     16: the fp8 GEMM over rotating copies of q (at least ROTATION_BYTES of them), the bf16 skinny GEMM over as many
     copies of W, and a device copy of q's bytes as the yardstick.  Whole step: ``decode_step(gemm="skinny")`` on the
     bf16 weights against the same on a snapshot, ABBA as in bench_step; the time of quantize_projections and the
-    snapshot's bytes."""
+    snapshot's bytes.  The same at M = 17, 32 and 64 for the 17-to-64-row kernels: toa_gemm_stream_w8 against
+    toa_gemm_stream, which is what ran these operands before it; and the whole call, Llama.extend of 8 rows x 4
+    tokens under ``stream`` on the bf16 weights against the same on the snapshot, ABBA."""
     from tf_operator_amd.models.llama import PRESETS, Llama
     from tf_operator_amd.ops import _lib, gemm
 
@@ -218,7 +223,26 @@ def bench_fp8(a, dev):
         ws8 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny_w8{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
         ws16 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
         wp, qp, sp = [P(w) for w in ws_], [P(q) for q, _ in pairs], [P(s) for _, s in pairs]
-        for M in MS:
+        res["stream_w8_split"] = _lib.call_ret("toa_gemm_stream_w8_split", rows, K)
+        res["stream_split"] = _lib.call_ret("toa_gemm_stream_split", N, K)
+        sws8 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_stream_w8{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        sws16 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_stream{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        for M in STREAM_W8_MS:
+            x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+
+            def stream_fp8(i):
+                _lib.call("toa_gemm_stream_w8" + tail, P(x), K, qp[i % copies], K, sp[i % copies], P(y), N, M, N, K,
+                          P(sws8), st)
+
+            def stream(i):
+                _lib.call("toa_gemm_stream" + tail, P(x), K, wp[i % copies], K, P(y), N, M, N, K, P(sws16), st)
+
+            arms = {"fp8": _row(*_sample_ms(stream_fp8, a.warmup, a.iters), qbytes, copy_med),
+                    "stream": _row(*_sample_ms(stream, a.warmup, a.iters), 2 * qbytes)}
+            arms["fp8_vs_stream"] = round(arms["stream"]["median_us"] / arms["fp8"]["median_us"], 3)
+            res[f"M{M}"] = arms
+        for M in MS if not a.only_stream else ():
             x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
             y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
 
@@ -252,7 +276,7 @@ def bench_fp8(a, dev):
     step = {"preset": "llama3-8b", "length": a.length, "steps_per_visit": STEPS, "rounds": a.rounds,
             "quantize_projections_ms": round(s.elapsed_time(e), 3),
             "snapshot_bytes": sum(q.numel() + 4 * sc.numel() for b in snap for q, sc in b.values())}
-    for B in (1, 8):
+    for B in (1, 8) if not a.only_stream else ():
         cache = m.new_cache(B, a.length + STEPS)
         tokens = torch.randint(0, m.cfg.vocab_size, (B,), device=dev)
 
@@ -278,7 +302,34 @@ def bench_fp8(a, dev):
         se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
         step[f"B{B}"] = {"skinny_ms_per_step": round(statistics.mean(t), 4), "fp8_ms_per_step": round(statistics.mean(f), 4),
                          "skinny_minus_fp8_ms": round(statistics.mean(d), 4), "stderr_ms": round(se, 4)}
-    assert not [k for k in gemm.fallbacks() if k.startswith("decode")]
+    B, T = 8, 4
+    cache = m.new_cache(B, a.length + T)
+    tokens = torch.randint(0, m.cfg.vocab_size, (B, T), device=dev)
+
+    def call(weights):
+        cache.set_lengths([a.length] * B)
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        with torch.no_grad():
+            m.extend(tokens, cache, gemm="stream", logits="last", weights=weights)
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e)
+
+    for w in (None, snap, None, snap):
+        call(w)   # warm-up: code objects, workspaces, allocator
+    t, f, d = [], [], []
+    for _ in range(a.rounds):
+        r = [call(w) for w in (None, snap, snap, None)]
+        t.append((r[0] + r[3]) / 2)
+        f.append((r[1] + r[2]) / 2)
+        d.append(t[-1] - f[-1])
+    se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
+    out["extend"] = {"preset": "llama3-8b", "B": B, "T": T, "length": a.length, "rounds": a.rounds,
+                     "stream_ms": round(statistics.mean(t), 4), "fp8_ms": round(statistics.mean(f), 4),
+                     "stream_minus_fp8_ms": round(statistics.mean(d), 4), "stderr_ms": round(se, 4)}
+    assert not [k for k in gemm.fallbacks() if k.startswith("decode")], gemm.fallbacks()
     out["step"] = step
     return out
 

@@ -388,9 +388,10 @@ class Llama(torch.nn.Module):
         raises ValueError before a launch.
 
         weights: None, or a snapshot from :meth:`quantize_projections`: the
-        blocks' projections of up to 16 rows then run on the fp8 weights
-        (ops.gemm linear_skinny_w8 / swiglu_skinny_w8: half the weight bytes);
-        operands that GEMM refuses take the bf16 weight by `gemm` and are
+        blocks' projections of up to 16 rows, and of 17 to 64 rows under
+        ``stream``, then run on the fp8 weights (ops.gemm linear_skinny_w8 /
+        swiglu_skinny_w8, linear_stream_w8 / swiglu_stream_w8: half the weight
+        bytes); operands those GEMMs refuse take the bf16 weight by `gemm` and are
         counted (ops.gemm.fallbacks).  The head stays bf16.  A snapshot with
         ``gemm="tile"`` raises ValueError."""
         cfg = self.cfg

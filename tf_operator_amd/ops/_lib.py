@@ -211,6 +211,14 @@ _SIGS = {
     "toa_gemm_skinny_w8_split": [c_int, c_int],
     "toa_gemm_skinny_w8_slice_steps": [c_int, c_int],
     "toa_gemm_skinny_w8_constant": [c_int],
+    # fp8 weights, 17 to 64 rows (csrc/hip/gemm_stream_w8.hip, csrc/hip/gemm_stream_w8_shapes.h): the arguments of
+    # the 1-to-16-row GEMMs and of their check; the plan by the rows of q and K
+    "toa_gemm_stream_w8": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_stream_w8_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_stream_w8_check": [c_int] + [c_p] * 5 + [c_i64] * 4 + [c_int] * 3,
+    "toa_gemm_stream_w8_split": [c_int, c_int],
+    "toa_gemm_stream_w8_piece_chunks": [c_int, c_int],
+    "toa_gemm_stream_w8_constant": [c_int],
 }
 
 
@@ -253,11 +261,13 @@ def _load():
             sw.argtypes, sw.restype = [c_int], ctypes.c_char_p
         for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_stream_ws_bytes",
                      "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_skinny_w8_ws_bytes",
-                     "toa_gemm_skinny_w8_swiglu_ws_bytes"):
+                     "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_ws_bytes",
+                     "toa_gemm_stream_w8_swiglu_ws_bytes"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
-        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_kv_q8_why"):
+        for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_why",
+                     "toa_kv_q8_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -290,7 +300,8 @@ _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coher
                     "toa_wgrad_asm_workspace", "toa_gemm_shape_why", "toa_gemm_skinny_ws_bytes",
                     "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why", "toa_gemm_stream_ws_bytes",
                     "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why", "toa_gemm_skinny_w8_ws_bytes",
-                    "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why", "toa_kv_q8_why"}
+                    "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_ws_bytes",
+                    "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_why", "toa_kv_q8_why"}
 
 
 def _fn(name: str):

@@ -49,18 +49,22 @@ def check_gemm(gemm) -> str:
 
 
 def _w8(x, pair, swiglu, gemm):
-    """True when the fp8 pair (q, scale) of a weights snapshot serves these rows
-    (ops.gemm.skinny_w8_refusal: the launcher's own check).  Refused operands
-    -- more than 16 rows, say -- are counted (ops.gemm.fallbacks, warned once
-    per shape) and the caller goes on with the block's bf16 weight by `gemm`."""
+    """The fp8 kernel that serves these rows on the pair (q, scale) of a weights
+    snapshot: "skinny" (1 to 16 rows), "stream" (17 to 64 rows under
+    gemm="stream") or "" for none.  One check is asked per projection, the one
+    whose rows these are (ops.gemm.skinny_w8_refusal or stream_w8_refusal: the
+    launcher's own).  Refused operands -- more than 64 rows, or more than 16
+    under gemm="skinny" -- are counted (ops.gemm.fallbacks, warned once per
+    shape) and the caller goes on with the block's bf16 weight by `gemm`."""
     if pair is None:
-        return False
+        return ""
     if gemm == "tile":
         raise ValueError('a weights snapshot needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
-    why = _gemm.skinny_w8_refusal(x, pair[0], pair[1], swiglu)
+    kind = "stream" if gemm == "stream" and x.dim() == 2 and x.shape[0] > 16 else "skinny"
+    why = (_gemm.stream_w8_refusal if kind == "stream" else _gemm.skinny_w8_refusal)(x, pair[0], pair[1], swiglu)
     if why:
         _gemm._fallback("decode-fp8", (x.shape[0], pair[0].shape[0], x.shape[1]), f"bf16 {gemm}", why)
-    return not why
+    return "" if why else kind
 
 
 def project(x, w, gemm="tile", w8=None):
@@ -74,9 +78,11 @@ def project(x, w, gemm="tile", w8=None):
     take ops.gemm.linear_stream; only what both checks refuse takes the tile
     path and is counted.  w8: w's fp8 pair (q, scale) of a weights snapshot
     (Llama.quantize_projections); operands its check takes run on
-    ops.gemm.linear_skinny_w8 and w is not read."""
-    if _w8(x, w8, False, gemm):
-        return _gemm.linear_skinny_w8(x, *w8, checked=True)
+    ops.gemm.linear_skinny_w8 or, at 17 to 64 rows under ``stream``,
+    ops.gemm.linear_stream_w8, and w is not read."""
+    kind = _w8(x, w8, False, gemm)
+    if kind:
+        return (_gemm.linear_stream_w8 if kind == "stream" else _gemm.linear_skinny_w8)(x, *w8, checked=True)
     if gemm in ("skinny", "stream"):
         if w.shape[0] >= TILE_KEEPS_FROM and _gemm.asm_takes(x, w):
             return linear(x, w)   # the measured dispatch, not a fallback
@@ -97,9 +103,11 @@ def mlp(x, wgu, wd, gemm="tile", w8gu=None, w8d=None):
     [B, 2F] round trip), then the down projection; refused operands as in
     :func:`project`.  ``stream``: the same, with ops.gemm.swiglu_stream for
     17 to 64 rows.  w8gu, w8d: the fp8 pairs of wgu and wd, as in
-    :func:`project` (ops.gemm.swiglu_skinny_w8)."""
-    if _w8(x, w8gu, True, gemm):
-        return project(_gemm.swiglu_skinny_w8(x, *w8gu, checked=True), wd, gemm, w8d)
+    :func:`project` (ops.gemm.swiglu_skinny_w8, swiglu_stream_w8)."""
+    kind = _w8(x, w8gu, True, gemm)
+    if kind:
+        s = (_gemm.swiglu_stream_w8 if kind == "stream" else _gemm.swiglu_skinny_w8)(x, *w8gu, checked=True)
+        return project(s, wd, gemm, w8d)
     if gemm in ("skinny", "stream"):
         why = _gemm.skinny_refusal(x, wgu, swiglu=True)
         if not why:

@@ -710,15 +710,10 @@ def skinny_w8_why(reason: int) -> str:
     return _lib._fn("toa_gemm_skinny_w8_why")(reason).decode()
 
 
-def skinny_w8_refusal(x2, q, scale, swiglu: bool = False) -> str:
-    """Why (x2 [M, K], q [N, K] float8_e4m3fn, scale [N] fp32) are no operands
-    of the 1-to-16-row GEMM on fp8 weights, "" if they are: matrices with unit
-    column stride and a common K on one device, x2 bf16 on the GPU (any float
-    dtype on the CPU, which takes the fp32 reference), one contiguous fp32
-    scale per row of q, and a shape the launcher's check takes, in its own
-    words."""
-    if not _lib.has("toa_gemm_skinny_w8_check"):
-        return "library built without toa_gemm_skinny_w8"
+def _w8_refusal(kind, x2, q, scale, swiglu) -> str:
+    """The tensors' kind, which no launcher can see, then toa_gemm_<kind>_w8_check in its own words."""
+    if not _lib.has(f"toa_gemm_{kind}_w8_check"):
+        return f"library built without toa_gemm_{kind}_w8"
     for t in (x2, q):
         if t.dim() != 2:
             return f"a {t.dim()}-D tensor, not a matrix"
@@ -737,13 +732,23 @@ def skinny_w8_refusal(x2, q, scale, swiglu: bool = False) -> str:
     M, K = x2.shape
     N = q.shape[0] // 2 if swiglu else q.shape[0]
     # y and the workspace are the wrappers' own (contiguous, aligned): x2 stands in for them
-    r = _lib.call_ret("toa_gemm_skinny_w8_check", int(swiglu), x2.data_ptr(), q.data_ptr(), x2.data_ptr(),
+    r = _lib.call_ret(f"toa_gemm_{kind}_w8_check", int(swiglu), x2.data_ptr(), q.data_ptr(), x2.data_ptr(),
                       x2.data_ptr(), scale.data_ptr(), x2.stride(0), q.stride(0), N, q.shape[0], M, N, K)
-    return f"{skinny_w8_why(r)}: M={M} N={N} K={K}" if r else ""
+    return f"{_lib._fn(f'toa_gemm_{kind}_w8_why')(r).decode()}: M={M} N={N} K={K}" if r else ""
 
 
-def _skinny_w8_call(name, x2, q, scale, N, swiglu, checked):
-    r = "" if checked else skinny_w8_refusal(x2, q, scale, swiglu)
+def skinny_w8_refusal(x2, q, scale, swiglu: bool = False) -> str:
+    """Why (x2 [M, K], q [N, K] float8_e4m3fn, scale [N] fp32) are no operands
+    of the 1-to-16-row GEMM on fp8 weights, "" if they are: matrices with unit
+    column stride and a common K on one device, x2 bf16 on the GPU (any float
+    dtype on the CPU, which takes the fp32 reference), one contiguous fp32
+    scale per row of q, and a shape the launcher's check takes, in its own
+    words."""
+    return _w8_refusal("skinny", x2, q, scale, swiglu)
+
+
+def _w8_call(kind, name, x2, q, scale, N, swiglu, checked):
+    r = "" if checked else _w8_refusal(kind, x2, q, scale, swiglu)
     if r:
         raise ValueError(f"{name}: {r}")
     if not _lib.use_hip(x2):
@@ -757,6 +762,16 @@ def _skinny_w8_call(name, x2, q, scale, N, swiglu, checked):
     return y
 
 
+def _w8_linear_ref(x2, q, scale):
+    return ((x2.float() @ q.float().t()) * scale).to(x2.dtype)
+
+
+def _w8_swiglu_ref(x2, qgu, scale):
+    F_ = qgu.shape[0] // 2
+    gu = (x2.float() @ qgu.float().t()) * scale
+    return (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
+
+
 def linear_skinny_w8(x2: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
     """y [M, N] = scale * (x2 [M, K] q [N, K]^T) for M <= 16 on
     toa_gemm_skinny_w8: q converted to bf16 in registers (exact), fp32
@@ -765,20 +780,46 @@ def linear_skinny_w8(x2: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, che
     caller has just asked skinny_w8_refusal itself, ops.decode.project; the
     launcher still checks what it can see); CPU tensors take the fp32
     reference."""
-    y = _skinny_w8_call("toa_gemm_skinny_w8", x2, q, scale, q.shape[0], False, checked)
-    return ((x2.float() @ q.float().t()) * scale).to(x2.dtype) if y is None else y
+    y = _w8_call("skinny", "toa_gemm_skinny_w8", x2, q, scale, q.shape[0], False, checked)
+    return _w8_linear_ref(x2, q, scale) if y is None else y
 
 
 def swiglu_skinny_w8(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
     """s [M, F] = silu(g) * u, (g | u) = scale * (x2 qgu^T), qgu = gate | up
     [2F, K], for M <= 16 on toa_gemm_skinny_w8_swiglu: both accumulators are
     scaled in fp32, the product is rounded once; gu is never stored."""
-    F_ = qgu.shape[0] // 2
-    s = _skinny_w8_call("toa_gemm_skinny_w8_swiglu", x2, qgu, scale, F_, True, checked)
-    if s is None:
-        gu = (x2.float() @ qgu.float().t()) * scale
-        s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
-    return s
+    s = _w8_call("skinny", "toa_gemm_skinny_w8_swiglu", x2, qgu, scale, qgu.shape[0] // 2, True, checked)
+    return _w8_swiglu_ref(x2, qgu, scale) if s is None else s
+
+
+# ---- 17 to 64 rows on fp8 weights (csrc/hip/gemm_stream_w8.hip; what it takes is csrc/hip/gemm_stream_w8_shapes.h's
+# to say).  Twins of the four above.
+def stream_w8_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_stream_w8_why")(reason).decode()
+
+
+def stream_w8_refusal(x2, q, scale, swiglu: bool = False) -> str:
+    """Why (x2, q, scale) are no operands of the 17-to-64-row GEMM on fp8
+    weights, "" if they are; the rules of :func:`skinny_w8_refusal`, the
+    launcher's own words for the shape."""
+    return _w8_refusal("stream", x2, q, scale, swiglu)
+
+
+def linear_stream_w8(x2: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """y [M, N] = scale * (x2 [M, K] q [N, K]^T) for 17 <= M <= 64 on
+    toa_gemm_stream_w8: x staged in LDS, q converted to bf16 in registers
+    (exact), fp32 accumulation, one fp32 multiply by the scale, one rounding.
+    Refusals, ``checked`` and CPU tensors as in :func:`linear_skinny_w8`."""
+    y = _w8_call("stream", "toa_gemm_stream_w8", x2, q, scale, q.shape[0], False, checked)
+    return _w8_linear_ref(x2, q, scale) if y is None else y
+
+
+def swiglu_stream_w8(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """s [M, F] = silu(g) * u, (g | u) = scale * (x2 qgu^T), qgu = gate | up
+    [2F, K], for 17 <= M <= 64 on toa_gemm_stream_w8_swiglu: both accumulators
+    are scaled in fp32, the product is rounded once; gu is never stored."""
+    s = _w8_call("stream", "toa_gemm_stream_w8_swiglu", x2, qgu, scale, qgu.shape[0] // 2, True, checked)
+    return _w8_swiglu_ref(x2, qgu, scale) if s is None else s
 
 
 def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:

@@ -79,9 +79,9 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     weights: ``bf16``, ``fp8`` or a snapshot from Llama.quantize_projections
     (None: TOA_DECODE_WEIGHTS, default ``bf16``).  ``fp8`` quantises the
     blocks' projections once at the start of this call -- so a trainer samples
-    from its current weights -- and the decode steps of up to 16 rows read one
-    byte per weight (Llama.decode_step weights=); it needs gemm ``skinny`` or
-    ``stream``.
+    from its current weights -- and the decode steps and prefill chunks of up
+    to 16 rows (``stream``: up to 64) read one byte per weight
+    (Llama.decode_step weights=); it needs gemm ``skinny`` or ``stream``.
     kv: ``bf16`` or ``fp8`` (None: TOA_DECODE_KV, default ``bf16``): the KV
     cache in the model's dtype, or e4m3 keys and values with one power-of-two
     scale per token and KV head (Llama.new_cache(dtype=torch.float8_e4m3fn):

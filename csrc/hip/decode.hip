@@ -216,6 +216,26 @@ static void launch_decode(int GT, dim3 grid, hipStream_t stream, const bf16_t* q
 #undef TOA_DECODE_LAUNCH
 }
 
+// The main kernel alone: the partials of the nsplit splits into ws_o / ws_ml, unmerged (kv_cache.h; shared-prompt
+// decoding runs it on the rows' suffixes and merges them with the prefix's partials, decode_shared.hip).
+// Arguments are the entry points' to check.
+int kv_launch_decode_partials(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int* lens, float* ws_o,
+                              float* ws_ml, int B, int Hq, int Hkv, int C, int D, int split_keys, int nsplit,
+                              float scale, hipStream_t stream) {
+  const int G = Hq / Hkv;
+  int GT = 8;
+  while (G % GT) GT >>= 1;  // the largest power of two <= 8 that divides the group
+  const int64_t gy = (int64_t)Hkv * (G / GT);
+  if (gy > 65535) return (int)hipErrorInvalidValue;
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const dim3 grid(nsplit, (unsigned)gy, B);
+  if (D == 128)
+    launch_decode<128>(GT, grid, stream, q, kc, vc, lens, ws_o, ws_ml, Hq, Hkv, C, split_keys, nsplit, scale_log2);
+  else
+    launch_decode<64>(GT, grid, stream, q, kc, vc, lens, ws_o, ws_ml, Hq, Hkv, C, split_keys, nsplit, scale_log2);
+  return (int)hipGetLastError();
+}
+
 // q [B, Hq, D], kc / vc [B, Hkv, C, D] bf16; lens [B] int32 (device); ws: fp32,
 // B Hq nsplit (D + 2) floats with nsplit = ceil(max_len / split_keys); o [B, Hq, D] bf16.
 // max_len: a host-side bound of len[b] (1 .. C) that sizes the grid; keys at or
@@ -226,21 +246,10 @@ extern "C" int toa_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* 
   if ((D != 64 && D != 128) || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return (int)hipErrorInvalidValue;
   if (split_keys < 64 || (split_keys & (split_keys - 1)) != 0) return (int)hipErrorInvalidValue;
   if (B <= 0 || B > 65535 || C <= 0 || max_len < 1 || max_len > C) return (int)hipErrorInvalidValue;
-  const int G = Hq / Hkv;
-  int GT = 8;
-  while (G % GT) GT >>= 1;  // the largest power of two <= 8 that divides the group
-  const int64_t gy = (int64_t)Hkv * (G / GT);
-  if (gy > 65535) return (int)hipErrorInvalidValue;
   const int nsplit = (max_len + split_keys - 1) / split_keys;
   float* ws_o = ws;
   float* ws_ml = ws + (int64_t)B * Hq * nsplit * D;
-  const float scale_log2 = scale * 1.4426950408889634f;
-  const dim3 grid(nsplit, (unsigned)gy, B);
-  if (D == 128)
-    launch_decode<128>(GT, grid, stream, q, kc, vc, lens, ws_o, ws_ml, Hq, Hkv, C, split_keys, nsplit, scale_log2);
-  else
-    launch_decode<64>(GT, grid, stream, q, kc, vc, lens, ws_o, ws_ml, Hq, Hkv, C, split_keys, nsplit, scale_log2);
-  int rc = (int)hipGetLastError();
+  int rc = kv_launch_decode_partials(q, kc, vc, lens, ws_o, ws_ml, B, Hq, Hkv, C, D, split_keys, nsplit, scale, stream);
   if (rc != 0) return rc;
   return kv_launch_split_merge(ws_o, ws_ml, lens, nullptr, o, B, 1, Hq, D, C, max_len, split_keys, nsplit, stream);
 }

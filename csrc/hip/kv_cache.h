@@ -65,6 +65,11 @@ int kv_launch_rope_append(const bf16_t* qkv, const float* cosv, const float* sin
                           bf16_t* q, bf16_t* kc, bf16_t* vc, int B, int T, int Hq, int Hkv, int D, int C,
                           int tab_rows, hipStream_t stream);
 
+// toa_attn_decode's main kernel alone (decode.hip): the partials of the rows' nsplit splits, unmerged.
+int kv_launch_decode_partials(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int* lens, float* ws_o,
+                              float* ws_ml, int B, int Hq, int Hkv, int C, int D, int split_keys, int nsplit,
+                              float scale, hipStream_t stream);
+
 // The splits of every query row -> o [B, T, Hq, D] bf16.  count != nullptr:
 // the row's last key is kv_token_last_key(start[b], count[b], t); nullptr
 // (decoding, T = 1): start holds the rows' lengths, kv_last_key(start[b]).

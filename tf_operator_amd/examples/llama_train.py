@@ -57,6 +57,9 @@ def main(argv=None):
                         "decoding) and prints one JSON line {\"sample\": {\"step\", \"tokens\"}}; 0 = never")
     p.add_argument("--sample-tokens", type=int, default=16, metavar="M", help="new tokens per sample")
     p.add_argument("--sample-prompt-len", type=int, default=8, metavar="P", help="prompt tokens per sample")
+    p.add_argument("--sample-count", type=int, default=1, metavar="N",
+                   help="completions per sample from one prefill and one copy of the prompt's keys (shared-prompt "
+                        "decoding, bf16 KV cache only); above 1 the JSON line also carries \"samples\", all N token rows")
     p.add_argument("--sample-gemm", choices=["tile", "skinny", "stream"], default=None,
                    help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
                         "weight-streaming GEMM for 1 to 16 rows (skinny), or that and its 17-to-64-row twin (stream); default: TOA_DECODE_GEMM, else tile")
@@ -84,6 +87,8 @@ def main(argv=None):
     a = p.parse_args(argv)
     if a.sample_every < 0 or a.sample_tokens < 1 or a.sample_prompt_len < 1:
         p.error("--sample-every needs N >= 0, --sample-tokens and --sample-prompt-len at least 1")
+    if a.sample_count < 1 or (a.sample_count > 1 and a.sample_kv == "fp8"):
+        p.error("--sample-count needs N >= 1, and --sample-kv bf16 above 1")
     if not (0.0 <= a.sample_temperature < float("inf")) or a.sample_top_k < 0:
         p.error("--sample-temperature needs a finite T >= 0, --sample-top-k needs K >= 0")
     if not 0.0 < a.sample_top_p <= 1.0 or not 0.0 <= a.sample_min_p < 1.0:
@@ -135,8 +140,12 @@ def _sample(a, tr, tokens):
     P = a.sample_prompt_len
     out, _ = tr.generate(tokens[:1, :P], a.sample_tokens, gemm=a.sample_gemm, prefill_chunk=a.sample_prefill_chunk,
                          temperature=a.sample_temperature, top_k=a.sample_top_k, top_p=a.sample_top_p,
-                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler, weights=a.sample_weights, kv=a.sample_kv)
-    print(json.dumps({"sample": {"step": tr.step_idx, "tokens": out[0, P:].tolist()}}), flush=True)
+                         min_p=a.sample_min_p, seed=a.sample_seed, sampler=a.sample_sampler, weights=a.sample_weights, kv=a.sample_kv,
+                         samples=a.sample_count)
+    rec = {"step": tr.step_idx, "tokens": out[0, P:].tolist()}
+    if a.sample_count > 1:
+        rec["samples"] = out[:, P:].tolist()
+    print(json.dumps({"sample": rec}), flush=True)
 
 
 def _train(a, rt, info):

@@ -200,6 +200,15 @@ class Llama(torch.nn.Module):
         return KVCache(self.cfg.layers, batch, self.cfg.kv_heads, capacity, self.cfg.head_dim,
                        w.device if device is None else device, w.dtype if dtype is None else dtype)
 
+    def new_shared_cache(self, groups, samples, prefix_capacity, capacity, device=None):
+        """An empty ops.decode.SharedKVCache of this model: `groups` prompts
+        of up to prefix_capacity tokens, `samples` completions each of up to
+        `capacity` generated tokens.  Prefill its ``prefix`` (:meth:`prefill`,
+        whole or by chunks), then :meth:`decode_step` on the cache itself."""
+        w = self.embed.weight
+        return _dec.SharedKVCache(self.cfg.layers, groups, samples, self.cfg.kv_heads, prefix_capacity, capacity,
+                                  self.cfg.head_dim, w.device if device is None else device, w.dtype)
+
     def _check_cache(self, cache, B):
         cfg = self.cfg
         if (cache.layers, cache.kv_heads, cache.head_dim) != (cfg.layers, cfg.kv_heads, cfg.head_dim):
@@ -345,6 +354,8 @@ class Llama(torch.nn.Module):
         B, T = tokens.shape
         gemm = check_gemm(gemm)
         self._check_weights(weights, gemm)
+        if isinstance(cache, _dec.SharedKVCache):
+            raise ValueError("extend on a SharedKVCache: extend its prefix before the first decode step instead")
         self._check_cache(cache, B)
         if logits not in ("last", "all"):
             raise ValueError(f"logits={logits!r}: expected 'last' or 'all'")
@@ -393,7 +404,15 @@ class Llama(torch.nn.Module):
         swiglu_skinny_w8, linear_stream_w8 / swiglu_stream_w8: half the weight
         bytes); operands those GEMMs refuse take the bf16 weight by `gemm` and are
         counted (ops.gemm.fallbacks).  The head stays bf16.  A snapshot with
-        ``gemm="tile"`` raises ValueError."""
+        ``gemm="tile"`` raises ValueError.
+
+        cache: a KVCache, or an ops.decode.SharedKVCache (new_shared_cache)
+        whose prefix holds the prompts: tokens [groups x samples], row
+        g samples + j the next token of sample j of prompt g.  Embedding,
+        norms, projections and head run on those rows as above; the new K and
+        V go to the rows' suffixes, rotated at prompt length + suffix slot,
+        and the attention reads each prompt's keys once for all its samples
+        (ops.decode.rope_append_shared / attn_decode_shared)."""
         cfg = self.cfg
         (B,) = tokens.shape
         gemm = check_gemm(gemm)
@@ -401,6 +420,8 @@ class Llama(torch.nn.Module):
         self._check_cache(cache, B)
         split_keys = check_split_keys(split_keys)
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        if isinstance(cache, _dec.SharedKVCache):
+            return self._decode_step_shared(tokens, cache, split_keys, gemm, weights)
         cos, sin, _ = self.rope(cache.capacity, tokens.device)
         cache.append()
         pos, lens, max_len = cache.positions, cache.lengths, cache.max_len
@@ -409,6 +430,26 @@ class Llama(torch.nn.Module):
             sc = cache.scales(i)
             q = rope_append(qkv, cos, sin, pos, cache.k[i], cache.v[i], Hq, Hkv, D, **sc)
             o = attn_decode(q, cache.k[i], cache.v[i], lens, split_keys=split_keys, max_len=max_len, **sc)
+            return o.view(B, Hq * D)
+
+        h, delta = self._cached_blocks(self.embed(tokens), attend, gemm, weights)
+        return self._logits_of(h, delta, gemm=gemm)
+
+    def _decode_step_shared(self, tokens, cache, split_keys, gemm, weights):
+        """decode_step on a SharedKVCache; arguments checked there."""
+        cfg = self.cfg
+        (B,) = tokens.shape
+        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        pre, suf, n = cache.prefix, cache.suffix, cache.samples
+        cos, sin, _ = self.rope(pre.capacity + suf.capacity, tokens.device)
+        cache.append()
+        base, max_plen = pre.lengths, pre.max_len
+        pos, lens, max_len = suf.positions, suf.lengths, suf.max_len
+
+        def attend(i, qkv):
+            q = _dec.rope_append_shared(qkv, cos, sin, base, pos, suf.k[i], suf.v[i], n, Hq, Hkv, D)
+            o = _dec.attn_decode_shared(q, pre.k[i], pre.v[i], base, suf.k[i], suf.v[i], lens, n,
+                                        split_keys=split_keys, max_prefix_len=max_plen, max_len=max_len)
             return o.view(B, Hq * D)
 
         h, delta = self._cached_blocks(self.embed(tokens), attend, gemm, weights)

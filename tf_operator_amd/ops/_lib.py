@@ -128,6 +128,12 @@ _SIGS = {
     "toa_attn_decode_q8": [c_p] * 8 + [c_int] * 7 + [c_f, c_p],
     "toa_attn_extend_q8": [c_p] * 9 + [c_int] * 8 + [c_f, c_p],
     "toa_kv_q8_check": [c_int] + [c_p] * 4 + [c_int] * 8,
+    # shared-prompt decoding (csrc/hip/decode_shared.hip, decode_shared_shapes.h): qkv cos sin base pos q kcache vcache,
+    # B samples Hq Hkv D C table_rows; q, prefix k v plen, suffix k v slen, workspace o, B groups samples Hq Hkv Cp Cs D
+    # max_plen max_slen split_keys scale.  The check: B groups samples Hq Hkv D Cp Cs max_plen max_slen split_keys
+    "toa_shared_rope_append": [c_p] * 8 + [c_int] * 7 + [c_p],
+    "toa_attn_decode_shared": [c_p] * 9 + [c_int] * 11 + [c_f, c_p],
+    "toa_decode_shared_check": [c_int] * 11,
     # sampling (csrc/hip/sample.hip): dtype logits ld, B V, temperature top_k top_p min_p stream_id position (per
     # row), seed, tokens, weights (or null), stream
     "toa_sample_tokens": [c_int, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_uint32, c_p, c_p,
@@ -267,7 +273,7 @@ def _load():
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
         for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_why",
-                     "toa_kv_q8_why"):
+                     "toa_kv_q8_why", "toa_decode_shared_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -301,7 +307,8 @@ _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coher
                     "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_skinny_why", "toa_gemm_stream_ws_bytes",
                     "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why", "toa_gemm_skinny_w8_ws_bytes",
                     "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_ws_bytes",
-                    "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_why", "toa_kv_q8_why"}
+                    "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_why", "toa_kv_q8_why",
+                    "toa_decode_shared_why"}
 
 
 def _fn(name: str):

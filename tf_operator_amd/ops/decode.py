@@ -6,7 +6,9 @@ HIP kernels: csrc/hip/decode.hip (``toa_decode_rope_append``,
 T tokens per row at once (chunked prefill, continuation), csrc/hip/extend.hip
 (``toa_extend_rope_append``, ``toa_attn_extend``: the same split on the MFMA);
 RoPE + append and the merge are one kernel each for both
-(csrc/hip/kv_cache.hip).  CPU tensors take a plain PyTorch reference (fp32
+(csrc/hip/kv_cache.hip); n samples per prompt on one copy of the prompt's keys
+are csrc/hip/decode_shared.hip (SharedKVCache, ``toa_shared_rope_append``,
+``toa_attn_decode_shared``).  CPU tensors take a plain PyTorch reference (fp32
 math, the result in the tensor's dtype), row by row, so the CPU tier runs the
 whole feature; decoding is its T = 1.
 
@@ -597,3 +599,156 @@ def attn_extend(q, k_cache, v_cache, start, count, scale=None, split_keys=None, 
     if k_scale is not None:
         k_cache, v_cache = dequantize_cache(k_cache, k_scale, q.dtype), dequantize_cache(v_cache, v_scale, q.dtype)
     return _attn_ref(q, k_cache, v_cache, start, count, max_len, scale)
+
+
+# ---- n samples per prompt on one prefix cache (csrc/hip/decode_shared.hip; docs/kernels.md "Shared prompts")
+class SharedKVCache:
+    """The cache of `samples` completions per prompt: ``prefix``, a KVCache of
+    `groups` rows (one per prompt, filled by Llama.prefill and read-only
+    afterwards), and ``suffix``, a KVCache of groups x samples rows that holds
+    only what was generated after the prompt; row g samples + j is sample j
+    of prompt g.  A decode step reads each prompt's keys once for all its
+    samples (ops.decode.attn_decode_shared).  The model's dtype only: the fp8
+    cache (float8_e4m3fn) is refused."""
+
+    def __init__(self, layers, groups, samples, kv_heads, prefix_capacity, capacity, head_dim, device,
+                 dtype=torch.bfloat16):
+        if dtype.itemsize < 2:
+            raise ValueError(f"SharedKVCache dtype {dtype}: the shared-prompt kernels read a cache of the model's dtype, "
+                             "not an fp8 one")
+        if min(groups, samples) < 1:
+            raise ValueError(f"SharedKVCache needs positive sizes (groups {groups}, samples {samples})")
+        self.prefix = KVCache(layers, groups, kv_heads, prefix_capacity, head_dim, device, dtype)
+        self.suffix = KVCache(layers, groups * samples, kv_heads, capacity, head_dim, device, dtype)
+        self.layers, self.groups, self.samples, self.batch = layers, groups, samples, groups * samples
+        self.kv_heads, self.head_dim, self.device, self.dtype = kv_heads, head_dim, self.prefix.device, dtype
+
+    def append(self, n=1):
+        """Every row's suffix grows by n slots; past its capacity: ValueError,
+        before any launch and with nothing changed."""
+        self.suffix.append(n)
+
+    def nbytes(self) -> int:
+        return self.prefix.nbytes() + self.suffix.nbytes()
+
+
+def _shared_call(name, args, B, groups, samples, Hq, Hkv, D, Cp, Cs, max_plen=0, max_slen=0, split=64):
+    """Launcher `name` of decode_shared.hip.  It refuses operands its check (decode_shared_shapes.h) does not take
+    before any launch; the same check, asked only then, names the reason: ValueError in its words."""
+    rc = _lib.call_ret(name, *args)
+    if rc == _gemm.HIP_ERROR_INVALID_VALUE:
+        r = _lib.call_ret("toa_decode_shared_check", B, groups, samples, Hq, Hkv, D, Cp, Cs, max_plen, max_slen, split)
+        raise ValueError(f"{name}: {_lib._fn('toa_decode_shared_why')(r).decode() if r else 'refused'}")
+    if rc:
+        raise RuntimeError(f"{name} failed with hipError {rc}")
+
+
+def _check_samples(samples, B):
+    if not isinstance(samples, int) or isinstance(samples, bool) or samples < 1 or B % samples:
+        raise ValueError(f"samples {samples!r}: a positive int that divides the {B} rows")
+    return B // samples
+
+
+def rope_append_shared(qkv, cos, sin, base, pos, k_cache, v_cache, samples, Hq, Hkv, D):
+    """rope_append with the rotation and the slot apart: qkv [B, (Hq + 2 Hkv) D],
+    B = groups x samples rows; base int32 [groups] (the prompts' lengths) and
+    pos int32 [B] (the slots of the suffix cache), both on the device.  Row b
+    rotates q and k at the absolute position base[b // samples] + pos[b] --
+    the bits rope_append gives at that position -- returns q [B, Hq, D] and
+    stores k and v into slot pos[b] of the suffix caches [B, Hkv, C, D]; no
+    other slot is written.  A slot outside the cache or a position outside
+    the table writes nothing to the caches and a zero q row."""
+    (pos,) = _check_rope(qkv, False, cos, sin, {"pos": pos}, k_cache, v_cache, Hq, Hkv, D)
+    B, C = qkv.shape[0], k_cache.shape[2]
+    groups = _check_samples(samples, B)
+    base = _check_rows("base", base, groups, qkv.device)
+    if _lib.use_hip(qkv):
+        _need_bf16("rope_append_shared", qkv)
+        qkv, cos, sin = qkv.contiguous(), cos.contiguous(), sin.contiguous()
+        q = torch.empty(B, Hq, D, device=qkv.device, dtype=qkv.dtype)
+        _shared_call("toa_shared_rope_append",
+                     (_lib.ptr(qkv), _lib.ptr(cos), _lib.ptr(sin), _lib.ptr(base), _lib.ptr(pos), _lib.ptr(q),
+                      _lib.ptr(k_cache), _lib.ptr(v_cache), B, samples, Hq, Hkv, D, C, cos.shape[0], _lib.stream(qkv)),
+                     B, groups, samples, Hq, Hkv, D, 1, C)
+        return q
+    # the plain reference at the absolute position, then the new rows moved to their slots: row by row, each on a
+    # one-slot view, so nothing else of the cache is touched
+    q = torch.zeros(B, 1, Hq, D, dtype=qkv.dtype)
+    for b, (s, bs) in enumerate(zip(pos.tolist(), base.repeat_interleave(samples).tolist())):
+        if not (0 <= s < C and bs >= 0 and bs + s < cos.shape[0]):
+            continue
+        one = torch.tensor([0], dtype=torch.int32)
+        q[b] = _rope_ref(qkv[b:b + 1, None], cos[bs + s:bs + s + 1], sin[bs + s:bs + s + 1], one, None,
+                         k_cache[b:b + 1, :, s:s + 1], v_cache[b:b + 1, :, s:s + 1], Hq, Hkv, D)[0]
+    return q[:, 0]
+
+
+def shared_ws_floats(B, Hq, D, max_plen, max_slen, split_keys) -> int:
+    """fp32 words of toa_attn_decode_shared's workspace: per (row, head) the partials of the prefix's and of the
+    suffix's splits, D + 2 words each."""
+    return B * Hq * (-(-max_plen // split_keys) + -(-max_slen // split_keys)) * (D + 2)
+
+
+def attn_decode_shared(q, prefix_k, prefix_v, prefix_lengths, k_cache, v_cache, lengths, samples, scale=None,
+                       split_keys=None, max_prefix_len=None, max_len=None, workspace=None):
+    """q [B, Hq, D], B = groups x samples, against the prompts' caches
+    prefix_k / prefix_v [groups, Hkv, Cp, D] and the rows' own k_cache /
+    v_cache [B, Hkv, Cs, D]: row b attends prefix keys
+    0 .. prefix_lengths[b // samples] - 1 and then its suffix keys
+    0 .. lengths[b] - 1 (int32 [groups] and [B] on the device) -- what
+    attn_decode computes on a cache holding the concatenation; returns
+    O [B, Hq, D].  An empty prefix or suffix contributes nothing; a row with
+    neither is zeros.
+
+    On the GPU: toa_attn_decode_shared.  The prefix runs on the MFMA, the
+    samples x (Hq / Hkv) query rows of a prompt and KV head against its keys,
+    split_keys keys per workgroup (a power of two >= 64; None:
+    SPLIT_KEYS_DEFAULT), every K / V byte read once per prompt; the suffix
+    runs attn_decode's kernel; one merge kernel.  max_prefix_len, max_len:
+    host-side bounds of the two lengths (None: the capacities) that size the
+    grids.  workspace: fp32, at least shared_ws_floats words (None:
+    torch.empty).  A row's result depends on its q, its prefix, its suffix,
+    the two lengths and split_keys only -- not on samples, its place in the
+    group or the other rows."""
+    split = check_split_keys(split_keys)
+    (lengths,), max_len, scale = _check_attn(q, False, k_cache, v_cache, {"lengths": lengths}, max_len, scale)
+    B, Hq, D = q.shape
+    Hkv, Cs = k_cache.shape[1], k_cache.shape[2]
+    groups = _check_samples(samples, B)
+    if prefix_k.dim() != 4:
+        raise ValueError(f"prefix_k {tuple(prefix_k.shape)} is not [groups, Hkv, Cp, D]")
+    _check_cache(prefix_k, prefix_v, groups, Hkv, D, q)
+    Cp = prefix_k.shape[2]
+    plens = _check_rows("prefix_lengths", prefix_lengths, groups, q.device)
+    max_plen = Cp if max_prefix_len is None else int(max_prefix_len)
+    if not 0 <= max_plen <= Cp:
+        raise ValueError(f"max_prefix_len {max_plen} outside 0 .. prefix capacity {Cp}")
+    words = shared_ws_floats(B, Hq, D, max_plen, max_len, split)
+    if workspace is not None:
+        if (workspace.dtype != torch.float32 or workspace.device != q.device or not workspace.is_contiguous()
+                or workspace.numel() < words or workspace.data_ptr() % 16):
+            raise ValueError(f"workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {words} words "
+                             f"on {q.device} (got {workspace.dtype} x {workspace.numel()} on {workspace.device})")
+    if _lib.use_hip(q):
+        _need_bf16("attn_decode_shared", q)
+        q = q.contiguous()
+        ws = torch.empty(words, device=q.device, dtype=torch.float32) if workspace is None else workspace
+        o = torch.empty_like(q)
+        _shared_call("toa_attn_decode_shared",
+                     (_lib.ptr(q), _lib.ptr(prefix_k), _lib.ptr(prefix_v), _lib.ptr(plens), _lib.ptr(k_cache),
+                      _lib.ptr(v_cache), _lib.ptr(lengths), _lib.ptr(ws), _lib.ptr(o), B, groups, samples, Hq, Hkv, Cp,
+                      Cs, D, max_plen, max_len, split, scale, _lib.stream(q)),
+                     B, groups, samples, Hq, Hkv, D, Cp, Cs, max_plen, max_len, split)
+        return o
+    # row by row on the concatenation of its prefix and its suffix: attn_decode's reference on that cache
+    out = torch.zeros_like(q)
+    pl = plens.clamp(0, max_plen).tolist()
+    for b, n in enumerate(lengths.clamp(0, max_len).tolist()):
+        p = pl[b // samples]
+        if p + n < 1:
+            continue
+        k = torch.cat([prefix_k[b // samples, :, :p], k_cache[b, :, :n]], 1)[None]
+        v = torch.cat([prefix_v[b // samples, :, :p], v_cache[b, :, :n]], 1)[None]
+        last = torch.tensor([p + n - 1], dtype=torch.int32)
+        out[b] = _attn_ref(q[b:b + 1, None], k, v, last, None, p + n, scale)[0, 0]
+    return out

@@ -58,7 +58,7 @@ def _pick(logits, temperature, top_k, gen):
 @torch.no_grad()
 def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, top_k=0, eos_id=None, seed=0,
              capacity=None, split_keys=None, gemm=None, prefill_chunk=None, top_p=1.0, min_p=0.0, sampler=None,
-             stream_ids=None, weights=None, kv=None):
+             stream_ids=None, weights=None, kv=None, samples=1):
     """prompts [B, P] token ids (ragged ones right-padded, lengths: host ints,
     default P each) -> (tokens [B, P + max_new_tokens], lengths int64 [B]):
     row b holds its prompt, then its max_new_tokens new tokens from position
@@ -94,12 +94,26 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     [B] tensors (a row at temperature 0 is greedy), and the draw is a hash of
     (seed, stream_ids[b], the row's cache length) -- no generator exists, and
     a row's tokens do not depend on the rows around it.  stream_ids: int64
-    [B], default arange(B)."""
+    [B], default arange(B).
+
+    samples=n > 1: n completions per prompt on one copy of the prompt's keys
+    and values (docs/kernels.md "Shared prompts").  The prompts [groups, P]
+    are prefilled once into the prefix of an ops.decode.SharedKVCache, the
+    logits repeated n times, and the steps decode groups x n rows; returns
+    tokens [groups n, P + max_new_tokens], row g n + j sample j of prompt g,
+    and their lengths -- the tokens of generate(prompts.repeat_interleave(n,
+    0), ...) under the torch sampler.  Per-row parameters and stream_ids
+    (default arange(groups n), so the samples draw differently) then have
+    groups n rows; capacity sizes the suffixes (default max_new_tokens).
+    kv="fp8" with samples > 1 raises ValueError."""
     if prompts.dim() != 2 or prompts.shape[1] < 1:
         raise ValueError(f"prompts {tuple(prompts.shape)} is not [B, P >= 1]")
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens {max_new_tokens} < 1")
-    B, P = prompts.shape
+    if not isinstance(samples, int) or isinstance(samples, bool) or samples < 1:
+        raise ValueError(f"samples {samples!r}: an int >= 1")
+    groups, P = prompts.shape
+    B = groups * samples
     dev = prompts.device
     sampler = check_sampler(sampler)
     if sampler == "device":
@@ -123,13 +137,19 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     gemm = check_gemm(gemm)
     weights = check_weights(weights)
     kv = check_kv(kv)
+    if samples > 1 and kv == "fp8":
+        raise ValueError('samples > 1 needs kv="bf16": the shared-prompt kernels read a cache of the model\'s dtype')
     if weights == "fp8" and gemm == "tile":
         raise ValueError('weights="fp8" needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
-    lengths = [P] * B if lengths is None else [int(n) for n in lengths]
-    if len(lengths) != B or min(lengths) < 1 or max(lengths) > P:
-        raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {B}")
+    lengths = [P] * groups if lengths is None else [int(n) for n in lengths]
+    if len(lengths) != groups or min(lengths) < 1 or max(lengths) > P:
+        raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {groups}")
     need = max(P, max(lengths) + max_new_tokens - 1)   # the last new token is never appended
-    capacity = P + max_new_tokens if capacity is None else int(capacity)
+    if samples > 1:   # the suffixes hold the new tokens only
+        need = max(max_new_tokens - 1, 1)
+        capacity = max_new_tokens if capacity is None else int(capacity)
+    else:
+        capacity = P + max_new_tokens if capacity is None else int(capacity)
     if capacity < need:
         raise ValueError(f"KV cache overflow: capacity {capacity} < {need} slots for prompts of up to {max(lengths)} "
                          f"tokens (padded to {P}) + {max_new_tokens} new ones")
@@ -140,7 +160,11 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
     weights = None if weights == "bf16" else model.quantize_projections() if weights == "fp8" else weights
-    cache = model.new_cache(B, capacity, device=dev, dtype=torch.float8_e4m3fn if kv == "fp8" else None)
+    if samples > 1:
+        cache = model.new_shared_cache(groups, samples, P, capacity, device=dev)
+        prompts, lengths = prompts.repeat_interleave(samples, 0), [n for n in lengths for _ in range(samples)]
+    else:
+        cache = model.new_cache(B, capacity, device=dev, dtype=torch.float8_e4m3fn if kv == "fp8" else None)
     pad = 0 if eos_id is None else int(eos_id)
     out = torch.full((B, P + max_new_tokens), pad, device=dev, dtype=prompts.dtype)
     cols = torch.arange(P + max_new_tokens, device=dev)
@@ -148,14 +172,23 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     out[:, :P] = torch.where(cols[None, :P] < at[:, None], prompts, out[:, :P])
     rows = torch.arange(B, device=dev)
     done = torch.zeros(B, device=dev, dtype=torch.bool)
-    logits = model.prefill(prompts, cache, lengths, gemm=gemm, chunk=prefill_chunk, weights=weights)
+    if samples > 1:   # a row's length: its prompt's plus its suffix's
+        plens = at.to(torch.int32)
+        positions = lambda: plens + cache.suffix.lengths
+    else:
+        positions = lambda: cache.lengths
+    if samples > 1:   # the prompts once, into the prefix; every sample starts from its prompt's logits
+        logits = model.prefill(prompts[::samples], cache.prefix, lengths[::samples], gemm=gemm, chunk=prefill_chunk,
+                               weights=weights).repeat_interleave(samples, 0)
+    else:
+        logits = model.prefill(prompts, cache, lengths, gemm=gemm, chunk=prefill_chunk, weights=weights)
     for t in range(max_new_tokens):
         if sampler == "torch":
             tok = _pick(logits, temperature, top_k, gen).to(prompts.dtype)
         elif greedy:
             tok = logits.argmax(-1).to(prompts.dtype)
         else:   # the cache's lengths: unique per row and step, on the device already
-            tok = _sample.sample_tokens(logits, seed=seed, stream_ids=stream_ids, positions=cache.lengths,
+            tok = _sample.sample_tokens(logits, seed=seed, stream_ids=stream_ids, positions=positions(),
                                         **rowp).to(prompts.dtype)
         if eos_id is not None:
             tok = torch.where(done, torch.full_like(tok, pad), tok)

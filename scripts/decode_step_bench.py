@@ -29,7 +29,12 @@ whole extend call on a snapshot (bench_fp8).  With ``--only-stream``: the
 17-to-64-row arms and the extend call alone.
 
     python scripts/decode_step_bench.py [--iters 50] [--rounds 8] [--skip-step] [--skip-forms] [--only-stream]
-                                        [--extend] [--fp8]
+                                        [--extend] [--fp8] [--wide]
+
+``--wide``: the 65-to-128-row GEMM (csrc/hip/gemm_wide.hip) per form at M = 65,
+96 and 128 against ``tile``, ``stream`` at M = 64, the decode step of 128 rows
+and a generate(samples=16) call on 8 prompts, ``wide`` against ``stream``
+(bench_wide).
 """
 import argparse
 import json
@@ -377,6 +382,116 @@ def bench_kv(a, dev):
     return out
 
 
+def _abba(visit, a_arm, b_arm, rounds):
+    """Arms a and b alternated ABBA: (mean a, mean b, mean of a - b per round, its standard error)."""
+    for arm in (a_arm, b_arm):
+        visit(arm)   # warm-up: code objects, workspaces, allocator
+    ta, tb, d = [], [], []
+    for _ in range(rounds):
+        r = [visit(arm) for arm in (a_arm, b_arm, b_arm, a_arm)]
+        ta.append((r[0] + r[3]) / 2)
+        tb.append((r[1] + r[2]) / 2)
+        d.append(ta[-1] - tb[-1])
+    se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
+    return (round(statistics.mean(ta), 4), round(statistics.mean(tb), 4), round(statistics.mean(d), 4), round(se, 4))
+
+
+def bench_wide(a, dev):
+    """The 65-to-128-row kernel (csrc/hip/gemm_wide.hip).  Per form, the four block projections at M = 65, 96 and
+    128: ``wide`` against ``tile`` (what ran these rows before it) and a device copy of W's bytes, and ``stream`` at
+    M = 64 for continuity; bench_forms' protocol.  Whole step: ``decode_step`` of 128 rows under ``wide`` against
+    ``stream`` (whose projections fall to ``tile`` there), ABBA; and one generate(samples=16) call on 8 prompts."""
+    from tf_operator_amd.models.llama import PRESETS, Llama
+    from tf_operator_amd.ops import _lib, gemm
+    from tf_operator_amd.train.generate import generate
+
+    P, st = _lib.ptr, _lib.stream()
+    forms = {}
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, swiglu in FORMS[:4] if not a.skip_forms else ():
+        rows = 2 * N if swiglu else N
+        nbytes = rows * K * 2
+        copies = max(2, -(-ROTATION_BYTES // nbytes))
+        ws_ = [(torch.randn(rows, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        dst = torch.empty_like(ws_[0])
+        wp = [P(w) for w in ws_]
+        tail = "_swiglu" if swiglu else ""
+        res = {"N": N, "K": K, "swiglu": swiglu, "W_bytes": nbytes, "copies": copies,
+               "wide_split": _lib.call_ret("toa_gemm_wide_split", rows, K)}
+        copy_med, lo, hi = _sample_ms(lambda i: dst.copy_(ws_[i % copies]), a.warmup, a.iters)
+        res["copy"] = _row(copy_med, lo, hi, nbytes)
+        wsb = max(int(_lib.call_ret(f"toa_gemm_wide{tail}_ws_bytes", N, K)),
+                  int(_lib.call_ret(f"toa_gemm_stream{tail}_ws_bytes", N, K)), 16)
+        ws = torch.empty(wsb // 4, device=dev, dtype=torch.float32)
+        for M in (64, 65, 96, 128):
+            x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            gu = torch.empty(M, 2 * N, device=dev, dtype=torch.bfloat16) if swiglu else None
+            kern = ("toa_gemm_stream" if M == 64 else "toa_gemm_wide") + tail
+
+            def stream_or_wide(i):
+                _lib.call(kern, P(x), K, wp[i % copies], K, P(y), N, M, N, K, P(ws), st)
+
+            def tile(i):
+                if swiglu:
+                    _lib.call("toa_gemm_asm_swiglu", P(x), K, wp[i % copies], K, P(gu), 2 * N, P(y), N, M, N, K, st)
+                else:
+                    _lib.call("toa_gemm_asm_rows", P(x), K, wp[i % copies], K, P(y), N, M, N, K, st)
+
+            arm = "stream" if M == 64 else "wide"
+            arms = {arm: _row(*_sample_ms(stream_or_wide, a.warmup, a.iters), nbytes, copy_med),
+                    "tile": _row(*_sample_ms(tile, a.warmup, a.iters), nbytes, copy_med)}
+            arms[arm + "_vs_tile"] = round(arms["tile"]["median_us"] / arms[arm]["median_us"], 3)
+            res[f"M{M}"] = arms
+        forms[name] = res
+        del ws_, dst
+        torch.cuda.empty_cache()
+    out = {"forms": forms}
+    if a.skip_step:
+        return out
+    m = Llama(PRESETS["llama3-8b"], device=dev)
+    m.init_weights(0)
+    m.eval()
+    B = 128
+    cache = m.new_cache(B, a.length + STEPS)
+    tokens = torch.randint(0, m.cfg.vocab_size, (B,), device=dev)
+
+    def visit(arm):
+        cache.set_lengths([a.length] * B)
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(STEPS):
+            m.decode_step(tokens, cache, gemm=arm)
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) / STEPS
+
+    gemm.reset_fallbacks()
+    visit("wide")
+    assert not [k for k in gemm.fallbacks() if k.startswith("decode")], gemm.fallbacks()
+    ts, tw, d, se = _abba(visit, "stream", "wide", a.rounds)
+    out["step"] = {"preset": "llama3-8b", "rows": B, "length": a.length, "steps_per_visit": STEPS, "rounds": a.rounds,
+                   "stream_ms_per_step": ts, "wide_ms_per_step": tw, "stream_minus_wide_ms": d, "stderr_ms": se}
+    del cache
+    torch.cuda.empty_cache()
+    prompts = torch.randint(0, m.cfg.vocab_size, (8, a.length), device=dev)
+
+    def sample(arm):
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        generate(m, prompts, STEPS, gemm=arm, samples=16)
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e)
+
+    ts, tw, d, se = _abba(sample, "stream", "wide", a.rounds)
+    out["generate"] = {"prompts": 8, "samples": 16, "prompt_len": a.length, "new_tokens": STEPS, "rounds": a.rounds,
+                       "stream_ms": ts, "wide_ms": tw, "stream_minus_wide_ms": d, "stderr_ms": se}
+    return out
+
+
 def bench_extend(a, dev):
     """Llama.extend of T = 4 tokens on B = 8 rows at cache length --len, logits="last": ``tile`` and ``stream``
     alternated ABBA, device events around each call; ms per call."""
@@ -426,6 +541,8 @@ def main(argv=None):
     ap.add_argument("--extend", action="store_true", help="the whole extend call, tile against stream")
     ap.add_argument("--fp8", action="store_true",
                     help="only the fp8 arm beside skinny: per form, the whole step (unless --skip-step), the quantiser")
+    ap.add_argument("--wide", action="store_true",
+                    help="only the 65-to-128-row arm: per form wide against tile, the 128-row step and generate call")
     ap.add_argument("--kv", action="store_true", help="only the whole step on the bf16 cache against the fp8 cache")
     a = ap.parse_args(argv)
     if a.iters < 50 or a.rounds < 8:
@@ -442,9 +559,11 @@ def main(argv=None):
         res["fp8"] = bench_fp8(a, dev)
     if a.kv:
         res["kv"] = bench_kv(a, dev)
-    if not a.skip_forms and not a.fp8 and not a.kv:
+    if a.wide:
+        res["wide"] = bench_wide(a, dev)
+    if not a.skip_forms and not a.fp8 and not a.kv and not a.wide:
         res["forms"] = bench_forms(a, dev)
-    if not a.skip_step and not a.fp8 and not a.kv:
+    if not a.skip_step and not a.fp8 and not a.kv and not a.wide:
         res["step"] = bench_step(a, dev)
     if a.extend:
         res["extend"] = bench_extend(a, dev)

@@ -60,12 +60,12 @@ def main(argv=None):
     p.add_argument("--sample-count", type=int, default=1, metavar="N",
                    help="completions per sample from one prefill and one copy of the prompt's keys (shared-prompt "
                         "decoding, bf16 KV cache only); above 1 the JSON line also carries \"samples\", all N token rows")
-    p.add_argument("--sample-gemm", choices=["tile", "skinny", "stream"], default=None,
+    p.add_argument("--sample-gemm", choices=["tile", "skinny", "stream", "wide"], default=None,
                    help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
-                        "weight-streaming GEMM for 1 to 16 rows (skinny), or that and its 17-to-64-row twin (stream); default: TOA_DECODE_GEMM, else tile")
+                        "weight-streaming GEMM for 1 to 16 rows (skinny), or that and its 17-to-64-row twin (stream), or both and the 65-to-128-row GEMM (wide); default: TOA_DECODE_GEMM, else tile")
     p.add_argument("--sample-weights", choices=["bf16", "fp8"], default=None,
                    help="what a sample's projections read: the bf16 weights, or an e4m3 copy quantised at the start of "
-                        "each sample (needs --sample-gemm skinny or stream); default: TOA_DECODE_WEIGHTS, else bf16")
+                        "each sample (needs --sample-gemm skinny, stream or wide); default: TOA_DECODE_WEIGHTS, else bf16")
     p.add_argument("--sample-kv", choices=["bf16", "fp8"], default=None,
                    help="a sample's KV cache: bf16, or e4m3 keys and values with one scale per token and KV head (half "
                         "the bytes); default: TOA_DECODE_KV, else bf16")

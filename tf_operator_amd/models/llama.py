@@ -338,7 +338,8 @@ class Llama(torch.nn.Module):
         to verify.  Embedding, norms and projections run on the B T rows
         (ops.decode.project / mlp by `gemm`, as in decode_step: the skinny
         GEMM applies by its own check when B T <= 16 and, under ``stream``,
-        the 17-to-64-row GEMM when B T is 17 to 64; refused operands take
+        the 17-to-64-row GEMM when B T is 17 to 64 and, under ``wide``, the
+        65-to-128-row GEMM when B T is 65 to 128; refused operands take
         ``tile`` and are counted), RoPE + append and the attention are
         ops.decode.rope_append_many / attn_extend (split_keys: None is
         ops.decode.extend_split's choice).  weights: as in decode_step.
@@ -395,12 +396,14 @@ class Llama(torch.nn.Module):
         linear_skinny / swiglu_skinny), the tile path for operands it
         refuses; ``stream``: ``skinny``, and for B of 17 to 64 rows the
         weight-streaming GEMM that stages x in LDS (linear_stream /
-        swiglu_stream); None: TOA_DECODE_GEMM, default ``tile``.  Anything else
+        swiglu_stream); ``wide``: ``stream``, and for B of 65 to 128 rows
+        the GEMM with two W tiles per wave (linear_wide / swiglu_wide);
+        None: TOA_DECODE_GEMM, default ``tile``.  Anything else
         raises ValueError before a launch.
 
         weights: None, or a snapshot from :meth:`quantize_projections`: the
         blocks' projections of up to 16 rows, and of 17 to 64 rows under
-        ``stream``, then run on the fp8 weights (ops.gemm linear_skinny_w8 /
+        ``stream`` or ``wide``, then run on the fp8 weights (ops.gemm linear_skinny_w8 /
         swiglu_skinny_w8, linear_stream_w8 / swiglu_stream_w8: half the weight
         bytes); operands those GEMMs refuse take the bf16 weight by `gemm` and are
         counted (ops.gemm.fallbacks).  The head stays bf16.  A snapshot with

@@ -207,6 +207,14 @@ _SIGS = {
     "toa_gemm_stream_split": [c_int, c_int],
     "toa_gemm_stream_piece_chunks": [c_int, c_int],
     "toa_gemm_stream_constant": [c_int],
+    # 65 to 128 rows (csrc/hip/gemm_wide.hip, csrc/hip/gemm_wide_shapes.h): the skinny launchers' arguments; the plan
+    # by the rows of W and K
+    "toa_gemm_wide": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_wide_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_wide_check": [c_int] + [c_p] * 4 + [c_i64] * 4 + [c_int] * 3,
+    "toa_gemm_wide_split": [c_int, c_int],
+    "toa_gemm_wide_piece_chunks": [c_int, c_int],
+    "toa_gemm_wide_constant": [c_int],
     # fp8 weights, 1 to 16 rows (csrc/hip/gemm_w8.hip, csrc/hip/gemm_w8_shapes.h).  The quantiser: w ldw q ldq (bytes)
     # scale, N K, stream.  The GEMMs: x ldx q ldw (bytes) scale y ldy, M N K, workspace, stream.  The check: form,
     # x q y workspace scale, ldx ldw ldy, rows behind q, M N K
@@ -268,12 +276,12 @@ def _load():
         for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_stream_ws_bytes",
                      "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_skinny_w8_ws_bytes",
                      "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_ws_bytes",
-                     "toa_gemm_stream_w8_swiglu_ws_bytes"):
+                     "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
         for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_why",
-                     "toa_kv_q8_why", "toa_decode_shared_why"):
+                     "toa_gemm_wide_why", "toa_kv_q8_why", "toa_decode_shared_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -308,7 +316,8 @@ _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coher
                     "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_stream_why", "toa_gemm_skinny_w8_ws_bytes",
                     "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_ws_bytes",
                     "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_why", "toa_kv_q8_why",
-                    "toa_decode_shared_why"}
+                    "toa_decode_shared_why", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes",
+                    "toa_gemm_wide_why"}
 
 
 def _fn(name: str):

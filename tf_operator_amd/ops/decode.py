@@ -35,7 +35,7 @@ E4M3 = torch.float8_e4m3fn   # the fp8 KV cache's bytes (csrc/hip/kv_cache_q8.hi
 SPLIT_KEYS_DEFAULT = 256
 
 
-GEMMS = ("tile", "skinny", "stream")   # what runs a decode step's projections (docs/kernels.md "Decoding")
+GEMMS = ("tile", "skinny", "stream", "wide")   # what runs a decode step's projections (docs/kernels.md "Decoding")
 # Under ``skinny``, a projection whose training GEMM already has a 256 x 256 tile per CU or more stays on it: at the
 # Llama-3-8B head (128256 x 4096, 501 tiles) the tile kernel measured 6 to 48 % faster than the skinny one at 1, 8 and
 # 16 rows on the same box; at the forms of 16 to 112 tiles it is 1.3 to 7.9 x slower (docs/kernels.md "Decoding").
@@ -53,7 +53,7 @@ def check_gemm(gemm) -> str:
 def _w8(x, pair, swiglu, gemm):
     """The fp8 kernel that serves these rows on the pair (q, scale) of a weights
     snapshot: "skinny" (1 to 16 rows), "stream" (17 to 64 rows under
-    gemm="stream") or "" for none.  One check is asked per projection, the one
+    gemm="stream" or "wide") or "" for none.  One check is asked per projection, the one
     whose rows these are (ops.gemm.skinny_w8_refusal or stream_w8_refusal: the
     launcher's own).  Refused operands -- more than 64 rows, or more than 16
     under gemm="skinny" -- are counted (ops.gemm.fallbacks, warned once per
@@ -62,7 +62,7 @@ def _w8(x, pair, swiglu, gemm):
         return ""
     if gemm == "tile":
         raise ValueError('a weights snapshot needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
-    kind = "stream" if gemm == "stream" and x.dim() == 2 and x.shape[0] > 16 else "skinny"
+    kind = "stream" if gemm in ("stream", "wide") and x.dim() == 2 and x.shape[0] > 16 else "skinny"
     why = (_gemm.stream_w8_refusal if kind == "stream" else _gemm.skinny_w8_refusal)(x, pair[0], pair[1], swiglu)
     if why:
         _gemm._fallback("decode-fp8", (x.shape[0], pair[0].shape[0], x.shape[1]), f"bf16 {gemm}", why)
@@ -78,23 +78,31 @@ def project(x, w, gemm="tile", w8=None):
     model) take the tile path and are counted (ops.gemm.fallbacks, warned
     once per shape).  ``stream``: as ``skinny``, and operands of 17 to 64 rows
     take ops.gemm.linear_stream; only what both checks refuse takes the tile
-    path and is counted.  w8: w's fp8 pair (q, scale) of a weights snapshot
+    path and is counted.  ``wide``: as ``stream``, and operands of 65 to 128
+    rows take ops.gemm.linear_wide; only what all three checks refuse takes
+    the tile path and is counted.  w8: w's fp8 pair (q, scale) of a weights snapshot
     (Llama.quantize_projections); operands its check takes run on
     ops.gemm.linear_skinny_w8 or, at 17 to 64 rows under ``stream``,
-    ops.gemm.linear_stream_w8, and w is not read."""
+    ops.gemm.linear_stream_w8, and w is not read; there is no fp8 kernel
+    above 64 rows, so under ``wide`` those rows are counted (``decode-fp8 ...
+    -> bf16 wide``) and run on w."""
     kind = _w8(x, w8, False, gemm)
     if kind:
         return (_gemm.linear_stream_w8 if kind == "stream" else _gemm.linear_skinny_w8)(x, *w8, checked=True)
-    if gemm in ("skinny", "stream"):
+    if gemm != "tile":
         if w.shape[0] >= TILE_KEEPS_FROM and _gemm.asm_takes(x, w):
             return linear(x, w)   # the measured dispatch, not a fallback
         why = _gemm.skinny_refusal(x, w)
         if not why:
             return _gemm.linear_skinny(x, w)
-        if gemm == "stream":
+        if gemm in ("stream", "wide"):
             why = _gemm.stream_refusal(x, w)
             if not why:
                 return _gemm.linear_stream(x, w)
+        if gemm == "wide":
+            why = _gemm.wide_refusal(x, w)
+            if not why:
+                return _gemm.linear_wide(x, w)
         _gemm._fallback("decode", (x.shape[0], w.shape[0], x.shape[1]), "tile", why)
     return linear(x, w)
 
@@ -104,20 +112,25 @@ def mlp(x, wgu, wd, gemm="tile", w8gu=None, w8d=None):
     SwiGLU in the gate|up GEMM (ops.gemm.swiglu_skinny: one launch, no
     [B, 2F] round trip), then the down projection; refused operands as in
     :func:`project`.  ``stream``: the same, with ops.gemm.swiglu_stream for
-    17 to 64 rows.  w8gu, w8d: the fp8 pairs of wgu and wd, as in
+    17 to 64 rows.  ``wide``: the same, with ops.gemm.swiglu_wide for 65 to
+    128 rows.  w8gu, w8d: the fp8 pairs of wgu and wd, as in
     :func:`project` (ops.gemm.swiglu_skinny_w8, swiglu_stream_w8)."""
     kind = _w8(x, w8gu, True, gemm)
     if kind:
         s = (_gemm.swiglu_stream_w8 if kind == "stream" else _gemm.swiglu_skinny_w8)(x, *w8gu, checked=True)
         return project(s, wd, gemm, w8d)
-    if gemm in ("skinny", "stream"):
+    if gemm != "tile":
         why = _gemm.skinny_refusal(x, wgu, swiglu=True)
         if not why:
             return project(_gemm.swiglu_skinny(x, wgu), wd, gemm, w8d)
-        if gemm == "stream":
+        if gemm in ("stream", "wide"):
             why = _gemm.stream_refusal(x, wgu, swiglu=True)
             if not why:
                 return project(_gemm.swiglu_stream(x, wgu), wd, gemm, w8d)
+        if gemm == "wide":
+            why = _gemm.wide_refusal(x, wgu, swiglu=True)
+            if not why:
+                return project(_gemm.swiglu_wide(x, wgu), wd, gemm, w8d)
         _gemm._fallback("decode", (x.shape[0], wgu.shape[0], x.shape[1]), "tile", why)
     return swiglu_mlp(x, wgu, wd)
 

@@ -645,6 +645,52 @@ def swiglu_stream(x2: torch.Tensor, wgu: torch.Tensor) -> torch.Tensor:
     return s
 
 
+# ---- 65 to 128 rows: the weight-streaming GEMM with two W tiles per wave on every x fragment (csrc/hip/gemm_wide.hip;
+# what it takes is csrc/hip/gemm_wide_shapes.h's to say).  Twins of the stream functions.
+def wide_reason(x2, w, swiglu: bool = False, y=None, ws=None) -> int:
+    """toa_gemm_wide_check, as :func:`skinny_reason`: 0 = taken, else the
+    reason :func:`wide_why` names."""
+    return _stream_reason("wide", x2, w, swiglu, y, ws)
+
+
+def wide_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_wide_why")(reason).decode()
+
+
+def wide_refusal(x2, w, swiglu: bool = False) -> str:
+    """Why (x2 [M, K], w [N, K]) are no operands of the 65-to-128-row GEMM, ""
+    if they are; the rules of :func:`skinny_refusal`, the launcher's own
+    words for the shape."""
+    return _stream_refusal("wide", x2, w, swiglu)
+
+
+def wide_takes(x2, w, swiglu: bool = False) -> bool:
+    """bf16 GPU matrices with unit column stride whose shape toa_gemm_wide_check accepts."""
+    return x2.is_cuda and w.is_cuda and not wide_refusal(x2, w, swiglu)
+
+
+def linear_wide(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """y [M, N] = x2 [M, K] w [N, K]^T for 65 <= M <= 128 on toa_gemm_wide:
+    fp32 accumulation, one rounding.  Operands wide_refusal names raise
+    ValueError before a launch; CPU tensors take the fp32 reference."""
+    reading(w, "linear_wide")
+    y = _skinny_call("toa_gemm_wide", "toa_gemm_wide_ws_bytes", x2, w, w.shape[0], False, "wide")
+    return (x2.float() @ w.float().t()).to(x2.dtype) if y is None else y
+
+
+def swiglu_wide(x2: torch.Tensor, wgu: torch.Tensor) -> torch.Tensor:
+    """s [M, F] = silu(x2 Wg^T) * (x2 Wu^T), wgu = gate | up [2F, K], for
+    65 <= M <= 128 on toa_gemm_wide_swiglu: the product is taken from the
+    fp32 accumulators and rounded once; gu is never stored."""
+    reading(wgu, "swiglu_wide")
+    F_ = wgu.shape[0] // 2
+    s = _skinny_call("toa_gemm_wide_swiglu", "toa_gemm_wide_swiglu_ws_bytes", x2, wgu, F_, True, "wide")
+    if s is None:
+        gu = x2.float() @ wgu.float().t()
+        s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
+    return s
+
+
 # ---- 1 to 16 rows on fp8 weights (csrc/hip/gemm_w8.hip; what it takes is csrc/hip/gemm_w8_shapes.h's to say).
 # q [N, K] torch.float8_e4m3fn (OCP e4m3: largest finite 448), scale [N] fp32; y = bf16(scale * (x q^T)), fp32 sums.
 E4M3 = torch.float8_e4m3fn

@@ -71,7 +71,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     synchronises with the host.  capacity: the KV cache's (default: P +
     max_new_tokens); too small a one raises ValueError before any launch.
     gemm: what runs the projections of the decode steps and the prefill's head
-    (Llama.decode_step: ``tile``, ``skinny`` or ``stream``; None:
+    (Llama.decode_step: ``tile``, ``skinny``, ``stream`` or ``wide``; None:
     TOA_DECODE_GEMM, default ``tile``).
     prefill_chunk: Llama.prefill's chunk (None: the whole prompt at once
     through the training ops; n >= 1: n tokens at a time through the
@@ -81,7 +81,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     blocks' projections once at the start of this call -- so a trainer samples
     from its current weights -- and the decode steps and prefill chunks of up
     to 16 rows (``stream``: up to 64) read one byte per weight
-    (Llama.decode_step weights=); it needs gemm ``skinny`` or ``stream``.
+    (Llama.decode_step weights=); it needs gemm ``skinny``, ``stream`` or ``wide``.
     kv: ``bf16`` or ``fp8`` (None: TOA_DECODE_KV, default ``bf16``): the KV
     cache in the model's dtype, or e4m3 keys and values with one power-of-two
     scale per token and KV head (Llama.new_cache(dtype=torch.float8_e4m3fn):

@@ -34,7 +34,10 @@ whole extend call on a snapshot (bench_fp8).  With ``--only-stream``: the
 ``--wide``: the 65-to-128-row GEMM (csrc/hip/gemm_wide.hip) per form at M = 65,
 96 and 128 against ``tile``, ``stream`` at M = 64, the decode step of 128 rows
 and a generate(samples=16) call on 8 prompts, ``wide`` against ``stream``
-(bench_wide).
+(bench_wide).  ``--wide --fp8``: the fp8 arm of that protocol alone, the
+65-to-128-row GEMM on fp8 weights (csrc/hip/gemm_wide_w8.hip) per form at
+M = 65, 96 and 128 against ``wide`` on the bf16 weights, and the decode step of
+128 rows on a snapshot against the same on the bf16 weights (bench_wide_fp8).
 """
 import argparse
 import json
@@ -492,6 +495,82 @@ def bench_wide(a, dev):
     return out
 
 
+def bench_wide_fp8(a, dev):
+    """The 65-to-128-row kernel on fp8 weights (csrc/hip/gemm_wide_w8.hip) against the bf16 ``wide`` kernel, which is
+    what ran these operands before it.  Per form, the four block projections at M = 65, 96 and 128: toa_gemm_wide_w8
+    over rotating copies of q (at least ROTATION_BYTES of them), toa_gemm_wide over as many copies of W, and a device
+    copy of q's bytes; bench_fp8's protocol.  Whole step: ``decode_step`` of 128 rows under ``wide`` on the bf16
+    weights against the same on a snapshot, ABBA."""
+    from tf_operator_amd.models.llama import PRESETS, Llama
+    from tf_operator_amd.ops import _lib, gemm
+
+    P, st = _lib.ptr, _lib.stream()
+    forms = {}
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, swiglu in FORMS[:4] if not a.skip_forms else ():
+        rows = 2 * N if swiglu else N
+        qbytes = rows * K
+        copies = max(2, -(-ROTATION_BYTES // qbytes))
+        ws_ = [(torch.randn(rows, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        pairs = [gemm.quantize_w8(w) for w in ws_]
+        dst = torch.empty_like(pairs[0][0])
+        tail = "_swiglu" if swiglu else ""
+        res = {"N": N, "K": K, "swiglu": swiglu, "q_bytes": qbytes, "copies": copies,
+               "wide_w8_split": _lib.call_ret("toa_gemm_wide_w8_split", rows, K),
+               "wide_split": _lib.call_ret("toa_gemm_wide_split", rows, K)}
+        copy_med, lo, hi = _sample_ms(lambda i: dst.copy_(pairs[i % copies][0]), a.warmup, a.iters)
+        res["copy_q"] = _row(copy_med, lo, hi, qbytes)
+        ws8 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_wide_w8{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        ws16 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_wide{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        wp, qp, sp = [P(w) for w in ws_], [P(q) for q, _ in pairs], [P(s) for _, s in pairs]
+        for M in (65, 96, 128):
+            x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+
+            def fp8(i):
+                _lib.call("toa_gemm_wide_w8" + tail, P(x), K, qp[i % copies], K, sp[i % copies], P(y), N, M, N, K,
+                          P(ws8), st)
+
+            def wide(i):
+                _lib.call("toa_gemm_wide" + tail, P(x), K, wp[i % copies], K, P(y), N, M, N, K, P(ws16), st)
+
+            arms = {"fp8": _row(*_sample_ms(fp8, a.warmup, a.iters), qbytes, copy_med),
+                    "wide": _row(*_sample_ms(wide, a.warmup, a.iters), 2 * qbytes)}
+            arms["fp8_vs_wide"] = round(arms["wide"]["median_us"] / arms["fp8"]["median_us"], 3)
+            res[f"M{M}"] = arms
+        forms[name] = res
+        del ws_, pairs, dst
+        torch.cuda.empty_cache()
+    out = {"forms": forms}
+    if a.skip_step:
+        return out
+    m = Llama(PRESETS["llama3-8b"], device=dev)
+    m.init_weights(0)
+    m.eval()
+    snap = m.quantize_projections()
+    B = 128
+    cache = m.new_cache(B, a.length + STEPS)
+    tokens = torch.randint(0, m.cfg.vocab_size, (B,), device=dev)
+
+    def visit(weights):
+        cache.set_lengths([a.length] * B)
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(STEPS):
+            m.decode_step(tokens, cache, gemm="wide", weights=weights)
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) / STEPS
+
+    gemm.reset_fallbacks()
+    tw, tf, d, se = _abba(visit, None, snap, a.rounds)
+    assert not [k for k in gemm.fallbacks() if k.startswith("decode")], gemm.fallbacks()
+    out["step"] = {"preset": "llama3-8b", "rows": B, "length": a.length, "steps_per_visit": STEPS, "rounds": a.rounds,
+                   "wide_ms_per_step": tw, "fp8_ms_per_step": tf, "wide_minus_fp8_ms": d, "stderr_ms": se}
+    return out
+
+
 def bench_extend(a, dev):
     """Llama.extend of T = 4 tokens on B = 8 rows at cache length --len, logits="last": ``tile`` and ``stream``
     alternated ABBA, device events around each call; ms per call."""
@@ -555,12 +634,14 @@ def main(argv=None):
     gemm.resolve_auto()
     dev = torch.device("cuda", 0)
     res = {"device": torch.cuda.get_device_name(dev), "gemm_mode": gemm.mode(), "iters": a.iters, "inner": INNER}
-    if a.fp8:
+    if a.fp8 and a.wide:
+        res["wide_fp8"] = bench_wide_fp8(a, dev)
+    elif a.fp8:
         res["fp8"] = bench_fp8(a, dev)
+    elif a.wide:
+        res["wide"] = bench_wide(a, dev)
     if a.kv:
         res["kv"] = bench_kv(a, dev)
-    if a.wide:
-        res["wide"] = bench_wide(a, dev)
     if not a.skip_forms and not a.fp8 and not a.kv and not a.wide:
         res["forms"] = bench_forms(a, dev)
     if not a.skip_step and not a.fp8 and not a.kv and not a.wide:

@@ -402,10 +402,11 @@ class Llama(torch.nn.Module):
         raises ValueError before a launch.
 
         weights: None, or a snapshot from :meth:`quantize_projections`: the
-        blocks' projections of up to 16 rows, and of 17 to 64 rows under
-        ``stream`` or ``wide``, then run on the fp8 weights (ops.gemm linear_skinny_w8 /
-        swiglu_skinny_w8, linear_stream_w8 / swiglu_stream_w8: half the weight
-        bytes); operands those GEMMs refuse take the bf16 weight by `gemm` and are
+        blocks' projections of up to 16 rows, of 17 to 64 rows under
+        ``stream`` or ``wide``, and of 65 to 128 rows under ``wide``, then run
+        on the fp8 weights (ops.gemm linear_skinny_w8 / swiglu_skinny_w8,
+        linear_stream_w8 / swiglu_stream_w8, linear_wide_w8 / swiglu_wide_w8:
+        half the weight bytes); operands those GEMMs refuse take the bf16 weight by `gemm` and are
         counted (ops.gemm.fallbacks).  The head stays bf16.  A snapshot with
         ``gemm="tile"`` raises ValueError.
 

@@ -233,6 +233,13 @@ _SIGS = {
     "toa_gemm_stream_w8_split": [c_int, c_int],
     "toa_gemm_stream_w8_piece_chunks": [c_int, c_int],
     "toa_gemm_stream_w8_constant": [c_int],
+    # fp8 weights, 65 to 128 rows (csrc/hip/gemm_wide_w8.hip, csrc/hip/gemm_wide_w8_shapes.h): the same arguments
+    "toa_gemm_wide_w8": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_wide_w8_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_wide_w8_check": [c_int] + [c_p] * 5 + [c_i64] * 4 + [c_int] * 3,
+    "toa_gemm_wide_w8_split": [c_int, c_int],
+    "toa_gemm_wide_w8_piece_chunks": [c_int, c_int],
+    "toa_gemm_wide_w8_constant": [c_int],
 }
 
 
@@ -276,12 +283,13 @@ def _load():
         for name in ("toa_gemm_skinny_ws_bytes", "toa_gemm_skinny_swiglu_ws_bytes", "toa_gemm_stream_ws_bytes",
                      "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_skinny_w8_ws_bytes",
                      "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_ws_bytes",
-                     "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes"):
+                     "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes",
+                     "toa_gemm_wide_w8_ws_bytes", "toa_gemm_wide_w8_swiglu_ws_bytes"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
         for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_why",
-                     "toa_gemm_wide_why", "toa_kv_q8_why", "toa_decode_shared_why"):
+                     "toa_gemm_wide_why", "toa_gemm_wide_w8_why", "toa_kv_q8_why", "toa_decode_shared_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -317,7 +325,8 @@ _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coher
                     "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_ws_bytes",
                     "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_why", "toa_kv_q8_why",
                     "toa_decode_shared_why", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes",
-                    "toa_gemm_wide_why"}
+                    "toa_gemm_wide_why", "toa_gemm_wide_w8_ws_bytes", "toa_gemm_wide_w8_swiglu_ws_bytes",
+                    "toa_gemm_wide_w8_why"}
 
 
 def _fn(name: str):

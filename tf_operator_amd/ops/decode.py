@@ -53,20 +53,29 @@ def check_gemm(gemm) -> str:
 def _w8(x, pair, swiglu, gemm):
     """The fp8 kernel that serves these rows on the pair (q, scale) of a weights
     snapshot: "skinny" (1 to 16 rows), "stream" (17 to 64 rows under
-    gemm="stream" or "wide") or "" for none.  One check is asked per projection, the one
-    whose rows these are (ops.gemm.skinny_w8_refusal or stream_w8_refusal: the
-    launcher's own).  Refused operands -- more than 64 rows, or more than 16
-    under gemm="skinny" -- are counted (ops.gemm.fallbacks, warned once per
-    shape) and the caller goes on with the block's bf16 weight by `gemm`."""
+    gemm="stream" or "wide"), "wide" (65 to 128 rows under gemm="wide") or ""
+    for none.  One check is asked per projection, the one whose rows these are
+    (ops.gemm.skinny_w8_refusal, stream_w8_refusal or wide_w8_refusal: the
+    launcher's own).  Refused operands -- more than 128 rows, more than 64
+    under gemm="stream", or more than 16 under gemm="skinny" -- are counted
+    (ops.gemm.fallbacks, warned once per shape) and the caller goes on with
+    the block's bf16 weight by `gemm`."""
     if pair is None:
         return ""
     if gemm == "tile":
         raise ValueError('a weights snapshot needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
-    kind = "stream" if gemm in ("stream", "wide") and x.dim() == 2 and x.shape[0] > 16 else "skinny"
-    why = (_gemm.stream_w8_refusal if kind == "stream" else _gemm.skinny_w8_refusal)(x, pair[0], pair[1], swiglu)
+    rows = x.shape[0] if x.dim() == 2 else 0
+    kind = "wide" if gemm == "wide" and rows > 64 else "stream" if gemm in ("stream", "wide") and rows > 16 else "skinny"
+    why = _W8_REFUSAL[kind](x, pair[0], pair[1], swiglu)
     if why:
         _gemm._fallback("decode-fp8", (x.shape[0], pair[0].shape[0], x.shape[1]), f"bf16 {gemm}", why)
     return "" if why else kind
+
+
+# the fp8 kernels by the rows they serve: the launcher's check, the plain form, the SwiGLU form
+_W8_REFUSAL = {"skinny": _gemm.skinny_w8_refusal, "stream": _gemm.stream_w8_refusal, "wide": _gemm.wide_w8_refusal}
+_W8_LINEAR = {"skinny": _gemm.linear_skinny_w8, "stream": _gemm.linear_stream_w8, "wide": _gemm.linear_wide_w8}
+_W8_SWIGLU = {"skinny": _gemm.swiglu_skinny_w8, "stream": _gemm.swiglu_stream_w8, "wide": _gemm.swiglu_wide_w8}
 
 
 def project(x, w, gemm="tile", w8=None):
@@ -82,13 +91,14 @@ def project(x, w, gemm="tile", w8=None):
     rows take ops.gemm.linear_wide; only what all three checks refuse takes
     the tile path and is counted.  w8: w's fp8 pair (q, scale) of a weights snapshot
     (Llama.quantize_projections); operands its check takes run on
-    ops.gemm.linear_skinny_w8 or, at 17 to 64 rows under ``stream``,
-    ops.gemm.linear_stream_w8, and w is not read; there is no fp8 kernel
-    above 64 rows, so under ``wide`` those rows are counted (``decode-fp8 ...
-    -> bf16 wide``) and run on w."""
+    ops.gemm.linear_skinny_w8, at 17 to 64 rows under ``stream`` or ``wide``
+    ops.gemm.linear_stream_w8, at 65 to 128 rows under ``wide``
+    ops.gemm.linear_wide_w8, and w is not read; there is no fp8 kernel above
+    128 rows (above 64 under ``stream``), so those rows are counted
+    (``decode-fp8 ... -> bf16 wide``, ``-> bf16 stream``) and run on w."""
     kind = _w8(x, w8, False, gemm)
     if kind:
-        return (_gemm.linear_stream_w8 if kind == "stream" else _gemm.linear_skinny_w8)(x, *w8, checked=True)
+        return _W8_LINEAR[kind](x, *w8, checked=True)
     if gemm != "tile":
         if w.shape[0] >= TILE_KEEPS_FROM and _gemm.asm_takes(x, w):
             return linear(x, w)   # the measured dispatch, not a fallback
@@ -114,10 +124,11 @@ def mlp(x, wgu, wd, gemm="tile", w8gu=None, w8d=None):
     :func:`project`.  ``stream``: the same, with ops.gemm.swiglu_stream for
     17 to 64 rows.  ``wide``: the same, with ops.gemm.swiglu_wide for 65 to
     128 rows.  w8gu, w8d: the fp8 pairs of wgu and wd, as in
-    :func:`project` (ops.gemm.swiglu_skinny_w8, swiglu_stream_w8)."""
+    :func:`project` (ops.gemm.swiglu_skinny_w8, swiglu_stream_w8,
+    swiglu_wide_w8)."""
     kind = _w8(x, w8gu, True, gemm)
     if kind:
-        s = (_gemm.swiglu_stream_w8 if kind == "stream" else _gemm.swiglu_skinny_w8)(x, *w8gu, checked=True)
+        s = _W8_SWIGLU[kind](x, *w8gu, checked=True)
         return project(s, wd, gemm, w8d)
     if gemm != "tile":
         why = _gemm.skinny_refusal(x, wgu, swiglu=True)

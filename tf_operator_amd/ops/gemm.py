@@ -868,6 +868,37 @@ def swiglu_stream_w8(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, c
     return _w8_swiglu_ref(x2, qgu, scale) if s is None else s
 
 
+# ---- 65 to 128 rows on fp8 weights (csrc/hip/gemm_wide_w8.hip; what it takes is csrc/hip/gemm_wide_w8_shapes.h's to
+# say).  Twins of the four above.
+def wide_w8_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_wide_w8_why")(reason).decode()
+
+
+def wide_w8_refusal(x2, q, scale, swiglu: bool = False) -> str:
+    """Why (x2, q, scale) are no operands of the 65-to-128-row GEMM on fp8
+    weights, "" if they are; the rules of :func:`skinny_w8_refusal`, the
+    launcher's own words for the shape."""
+    return _w8_refusal("wide", x2, q, scale, swiglu)
+
+
+def linear_wide_w8(x2: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """y [M, N] = scale * (x2 [M, K] q [N, K]^T) for 65 <= M <= 128 on
+    toa_gemm_wide_w8: x staged in LDS, q converted to bf16 in registers
+    (exact), two row tiles of q per wave on every x fragment, fp32
+    accumulation, one fp32 multiply by the scale, one rounding.  Refusals,
+    ``checked`` and CPU tensors as in :func:`linear_skinny_w8`."""
+    y = _w8_call("wide", "toa_gemm_wide_w8", x2, q, scale, q.shape[0], False, checked)
+    return _w8_linear_ref(x2, q, scale) if y is None else y
+
+
+def swiglu_wide_w8(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """s [M, F] = silu(g) * u, (g | u) = scale * (x2 qgu^T), qgu = gate | up
+    [2F, K], for 65 <= M <= 128 on toa_gemm_wide_w8_swiglu: both accumulators
+    are scaled in fp32, the product is rounded once; gu is never stored."""
+    s = _w8_call("wide", "toa_gemm_wide_w8_swiglu", x2, qgu, scale, qgu.shape[0] // 2, True, checked)
+    return _w8_swiglu_ref(x2, qgu, scale) if s is None else s
+
+
 def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:
     """toa_gemm_shape_check for g [N, K] (+)= dy2 [T, N]^T x2 [T, K] on the
     assembly ("wgrad_asm") or the HIP ("wgrad_hip") kernel.  g stands in for

@@ -80,7 +80,7 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     (None: TOA_DECODE_WEIGHTS, default ``bf16``).  ``fp8`` quantises the
     blocks' projections once at the start of this call -- so a trainer samples
     from its current weights -- and the decode steps and prefill chunks of up
-    to 16 rows (``stream``: up to 64) read one byte per weight
+    to 16 rows (``stream``: up to 64, ``wide``: up to 128) read one byte per weight
     (Llama.decode_step weights=); it needs gemm ``skinny``, ``stream`` or ``wide``.
     kv: ``bf16`` or ``fp8`` (None: TOA_DECODE_KV, default ``bf16``): the KV
     cache in the model's dtype, or e4m3 keys and values with one power-of-two

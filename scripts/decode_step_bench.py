@@ -22,14 +22,16 @@ whatever the host's launch cost leaves exposed.
 
 One JSON line.
 
-``--fp8``: the 1-to-16-row GEMM on fp8 weights (csrc/hip/gemm_w8.hip) beside
+``--fp4``: the 1-to-16-row GEMM on MXFP4 weights (csrc/hip/gemm_w4.hip) beside
+the fp8 and bf16 ones per form, and the whole step on an fp4 snapshot against
+an fp8 one (bench_fp4).  ``--fp8``: the 1-to-16-row GEMM on fp8 weights (csrc/hip/gemm_w8.hip) beside
 ``skinny`` and the 17-to-64-row one (csrc/hip/gemm_stream_w8.hip) beside
 ``stream``, per form against a copy of q's bytes, and as a whole step and a
 whole extend call on a snapshot (bench_fp8).  With ``--only-stream``: the
 17-to-64-row arms and the extend call alone.
 
     python scripts/decode_step_bench.py [--iters 50] [--rounds 8] [--skip-step] [--skip-forms] [--only-stream]
-                                        [--extend] [--fp8] [--wide]
+                                        [--extend] [--fp8] [--fp4] [--wide]
 
 ``--wide``: the 65-to-128-row GEMM (csrc/hip/gemm_wide.hip) per form at M = 65,
 96 and 128 against ``tile``, ``stream`` at M = 64, the decode step of 128 rows
@@ -342,6 +344,110 @@ def bench_fp8(a, dev):
     return out
 
 
+def bench_fp4(a, dev):
+    """The MXFP4 arm (csrc/hip/gemm_w4.hip) beside the fp8 kernel, which is what ran these operands before it, and
+    bf16 ``skinny``; bench_fp8's protocol.  Per form at M = 1, 8 and 16: the fp4 GEMM over rotating copies of q and
+    its scales (at least ROTATION_BYTES of them), the fp8 and bf16 GEMMs over as many copies of theirs, and a device
+    copy of the fp4 bytes as the yardstick.  Whole step: ``decode_step(gemm="skinny")`` on an fp8 snapshot against the
+    same on an fp4 one, ABBA; the time of quantize_projections(fmt="fp4") and the snapshot's bytes."""
+    from tf_operator_amd.models.llama import PRESETS, Llama
+    from tf_operator_amd.ops import _lib, gemm
+
+    P, st = _lib.ptr, _lib.stream()
+    forms = {}
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, swiglu in FORMS[:4]:
+        rows = 2 * N if swiglu else N
+        qbytes = rows * (K // 2 + K // 32)
+        copies = max(2, -(-ROTATION_BYTES // qbytes))
+        ws_ = [(torch.randn(rows, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        p8, p4 = [gemm.quantize_w8(w) for w in ws_], [gemm.quantize_w4(w) for w in ws_]
+        lds = p4[0][1].stride(0)
+        src = [torch.empty(qbytes, device=dev, dtype=torch.uint8) for _ in range(copies)]   # q and scales, one buffer
+        dst = torch.empty_like(src[0])
+        res = {"N": N, "K": K, "swiglu": swiglu, "q_and_scale_bytes": qbytes, "copies": copies,
+               "split": _lib.call_ret("toa_gemm_skinny_w4_split", rows, K),
+               "fp8_split": _lib.call_ret("toa_gemm_skinny_w8_split", rows, K)}
+        copy_med, lo, hi = _sample_ms(lambda i: dst.copy_(src[i % copies]), a.warmup, a.iters)
+        res["copy"] = _row(copy_med, lo, hi, qbytes)
+        tail = "_swiglu" if swiglu else ""
+        ws4 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny_w4{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        ws8 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny_w8{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        ws16 = torch.empty(max(int(_lib.call_ret(f"toa_gemm_skinny{tail}_ws_bytes", N, K)), 16) // 4, device=dev)
+        wp = [P(w) for w in ws_]
+        for M in MS:
+            x = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+
+            def fp4(i):
+                q, s = p4[i % copies]
+                _lib.call("toa_gemm_skinny_w4" + tail, P(x), K, P(q), K // 2, P(s), lds, P(y), N, M, N, K, P(ws4), st)
+
+            def fp8(i):
+                q, s = p8[i % copies]
+                _lib.call("toa_gemm_skinny_w8" + tail, P(x), K, P(q), K, P(s), P(y), N, M, N, K, P(ws8), st)
+
+            def skinny(i):
+                _lib.call("toa_gemm_skinny" + tail, P(x), K, wp[i % copies], K, P(y), N, M, N, K, P(ws16), st)
+
+            arms = {"fp4": _row(*_sample_ms(fp4, a.warmup, a.iters), qbytes, copy_med),
+                    "fp8": _row(*_sample_ms(fp8, a.warmup, a.iters), rows * K),
+                    "skinny": _row(*_sample_ms(skinny, a.warmup, a.iters), 2 * rows * K)}
+            arms["fp4_vs_fp8"] = round(arms["fp8"]["median_us"] / arms["fp4"]["median_us"], 3)
+            arms["fp4_vs_skinny"] = round(arms["skinny"]["median_us"] / arms["fp4"]["median_us"], 3)
+            res[f"M{M}"] = arms
+        forms[name] = res
+        del ws_, p8, p4, src, dst
+        torch.cuda.empty_cache()
+    out = {"forms": forms}
+    if a.skip_step:
+        return out
+    m = Llama(PRESETS["llama3-8b"], device=dev)
+    m.init_weights(0)
+    m.eval()
+    m.quantize_projections(fmt="fp4")   # warm-up
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    snap4 = m.quantize_projections(fmt="fp4")
+    e.record()
+    e.synchronize()
+    snap8 = m.quantize_projections()
+    step = {"preset": "llama3-8b", "length": a.length, "steps_per_visit": STEPS, "rounds": a.rounds,
+            "quantize_projections_fp4_ms": round(s.elapsed_time(e), 3),
+            "fp4_snapshot_bytes": sum(q.numel() + sc.numel() for b in snap4 for q, sc in b.values()),
+            "fp8_snapshot_bytes": sum(q.numel() + 4 * sc.numel() for b in snap8 for q, sc in b.values())}
+    for B in (1, 8):
+        cache = m.new_cache(B, a.length + STEPS)
+        tokens = torch.randint(0, m.cfg.vocab_size, (B,), device=dev)
+
+        def visit(weights):
+            cache.set_lengths([a.length] * B)
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(STEPS):
+                m.decode_step(tokens, cache, gemm="skinny", weights=weights)
+            e.record()
+            e.synchronize()
+            return s.elapsed_time(e) / STEPS
+
+        for w in (snap8, snap4):
+            visit(w)   # warm-up: code objects, workspaces, allocator
+        t, f, d = [], [], []
+        for _ in range(a.rounds):
+            r = [visit(w) for w in (snap8, snap4, snap4, snap8)]
+            t.append((r[0] + r[3]) / 2)
+            f.append((r[1] + r[2]) / 2)
+            d.append(t[-1] - f[-1])
+        se = statistics.stdev(d) / len(d) ** 0.5 if len(d) > 1 else float("nan")
+        step[f"B{B}"] = {"fp8_ms_per_step": round(statistics.mean(t), 4), "fp4_ms_per_step": round(statistics.mean(f), 4),
+                         "fp8_minus_fp4_ms": round(statistics.mean(d), 4), "stderr_ms": round(se, 4)}
+    assert not [k for k in gemm.fallbacks() if k.startswith("decode")], gemm.fallbacks()
+    out["step"] = step
+    return out
+
+
 def bench_kv(a, dev):
     """The whole decode step on llama3-8b, ``skinny`` projections, B = 1 and 8 at cache length --len: the bf16 cache
     against the fp8 cache (csrc/hip/kv_cache_q8.hip), ABBA as in bench_step; ms per step and the caches' bytes."""
@@ -620,6 +726,9 @@ def main(argv=None):
     ap.add_argument("--extend", action="store_true", help="the whole extend call, tile against stream")
     ap.add_argument("--fp8", action="store_true",
                     help="only the fp8 arm beside skinny: per form, the whole step (unless --skip-step), the quantiser")
+    ap.add_argument("--fp4", action="store_true",
+                    help="only the MXFP4 arm beside fp8 and skinny: per form, the whole step against an fp8 snapshot "
+                         "(unless --skip-step), the quantiser")
     ap.add_argument("--wide", action="store_true",
                     help="only the 65-to-128-row arm: per form wide against tile, the 128-row step and generate call")
     ap.add_argument("--kv", action="store_true", help="only the whole step on the bf16 cache against the fp8 cache")
@@ -640,11 +749,13 @@ def main(argv=None):
         res["fp8"] = bench_fp8(a, dev)
     elif a.wide:
         res["wide"] = bench_wide(a, dev)
+    elif a.fp4:
+        res["fp4"] = bench_fp4(a, dev)
     if a.kv:
         res["kv"] = bench_kv(a, dev)
-    if not a.skip_forms and not a.fp8 and not a.kv and not a.wide:
+    if not a.skip_forms and not a.fp8 and not a.kv and not a.wide and not a.fp4:
         res["forms"] = bench_forms(a, dev)
-    if not a.skip_step and not a.fp8 and not a.kv and not a.wide:
+    if not a.skip_step and not a.fp8 and not a.kv and not a.wide and not a.fp4:
         res["step"] = bench_step(a, dev)
     if a.extend:
         res["extend"] = bench_extend(a, dev)

@@ -63,10 +63,11 @@ def main(argv=None):
     p.add_argument("--sample-gemm", choices=["tile", "skinny", "stream", "wide"], default=None,
                    help="what runs the projections of a sample's decode steps: the training GEMMs (tile) or the "
                         "weight-streaming GEMM for 1 to 16 rows (skinny), or that and its 17-to-64-row twin (stream), or both and the 65-to-128-row GEMM (wide); default: TOA_DECODE_GEMM, else tile")
-    p.add_argument("--sample-weights", choices=["bf16", "fp8"], default=None,
+    p.add_argument("--sample-weights", choices=["bf16", "fp8", "fp4"], default=None,
                    help="what a sample's projections read: the bf16 weights, or an e4m3 copy quantised at the start of "
                         "each sample (needs --sample-gemm skinny, stream or wide: fp8 kernels for up to 16, 64 or 128 "
-                        "rows); default: TOA_DECODE_WEIGHTS, else bf16")
+                        "rows), or an MXFP4 copy (fp4: a kernel for up to 16 rows); default: TOA_DECODE_WEIGHTS, else "
+                        "bf16")
     p.add_argument("--sample-kv", choices=["bf16", "fp8"], default=None,
                    help="a sample's KV cache: bf16, or e4m3 keys and values with one scale per token and KV head (half "
                         "the bytes); default: TOA_DECODE_KV, else bf16")

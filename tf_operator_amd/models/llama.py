@@ -228,17 +228,22 @@ class Llama(torch.nn.Module):
         return _dec.project(x, head, gemm)
 
     @torch.no_grad()
-    def quantize_projections(self):
+    def quantize_projections(self, fmt="fp8"):
         """A snapshot of the blocks' projections on fp8 weights
-        (ops.gemm.quantize_w8: e4m3 with one power-of-two scale per row): per
-        block a dict of (q, scale) for ``wqkv``, ``wo``, ``wgu`` and ``wd``,
-        half the bytes of the bf16 weights.  decode_step, extend, prefill and
+        (ops.gemm.quantize_w8: e4m3 with one power-of-two scale per row) or,
+        fmt="fp4", on MXFP4 weights (ops.gemm.quantize_w4: e2m1 pairs with one
+        e8m0 scale byte per block of 32): per block a dict of (q, scale) for
+        ``wqkv``, ``wo``, ``wgu`` and ``wd``, a half or 17/64 of the bytes of
+        the bf16 weights.  decode_step, extend, prefill and
         train.generate.generate take it as ``weights=``.  The head stays bf16.
         It is a copy: weights updated after the call are not in it."""
+        if fmt not in ("fp8", "fp4"):
+            raise ValueError(f"quantize_projections: fmt={fmt!r}, expected fp8 or fp4")
+        quantize = _gemm.quantize_w8 if fmt == "fp8" else _gemm.quantize_w4
         for blk in self.blocks:
             for n in W8_NAMES:
                 reading(getattr(blk, n), "quantize_projections")
-        return [{n: _gemm.quantize_w8(getattr(blk, n).detach()) for n in W8_NAMES} for blk in self.blocks]
+        return [{n: quantize(getattr(blk, n).detach()) for n in W8_NAMES} for blk in self.blocks]
 
     def _check_weights(self, weights, gemm):
         """weights=None, or a snapshot of this model under a weight-streaming `gemm`; else ValueError."""

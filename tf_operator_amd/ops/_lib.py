@@ -240,6 +240,16 @@ _SIGS = {
     "toa_gemm_wide_w8_split": [c_int, c_int],
     "toa_gemm_wide_w8_piece_chunks": [c_int, c_int],
     "toa_gemm_wide_w8_constant": [c_int],
+    # MXFP4 weights, 1 to 16 rows (csrc/hip/gemm_w4.hip, csrc/hip/gemm_w4_shapes.h).  The quantiser: w ldw q ldq
+    # (bytes) scale lds (bytes), N K, stream.  The GEMMs: x ldx q ldw scale lds y ldy, M N K, workspace, stream.  The
+    # check: form, x q y workspace scale, ldx ldw ldy lds, rows behind q, M N K
+    "toa_quant_w4": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_p],
+    "toa_gemm_skinny_w4": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_skinny_w4_swiglu": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p, c_p],
+    "toa_gemm_skinny_w4_check": [c_int] + [c_p] * 5 + [c_i64] * 5 + [c_int] * 3,
+    "toa_gemm_skinny_w4_split": [c_int, c_int],
+    "toa_gemm_skinny_w4_slice_steps": [c_int, c_int],
+    "toa_gemm_skinny_w4_constant": [c_int],
 }
 
 
@@ -284,12 +294,14 @@ def _load():
                      "toa_gemm_stream_swiglu_ws_bytes", "toa_gemm_skinny_w8_ws_bytes",
                      "toa_gemm_skinny_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_ws_bytes",
                      "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes",
-                     "toa_gemm_wide_w8_ws_bytes", "toa_gemm_wide_w8_swiglu_ws_bytes"):
+                     "toa_gemm_wide_w8_ws_bytes", "toa_gemm_wide_w8_swiglu_ws_bytes", "toa_gemm_skinny_w4_ws_bytes",
+                     "toa_gemm_skinny_w4_swiglu_ws_bytes"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int, c_int], c_i64
         for name in ("toa_gemm_skinny_why", "toa_gemm_stream_why", "toa_gemm_skinny_w8_why", "toa_gemm_stream_w8_why",
-                     "toa_gemm_wide_why", "toa_gemm_wide_w8_why", "toa_kv_q8_why", "toa_decode_shared_why"):
+                     "toa_gemm_wide_why", "toa_gemm_wide_w8_why", "toa_kv_q8_why", "toa_decode_shared_why",
+                     "toa_gemm_skinny_w4_why"):
             kw = getattr(lib, name, None)
             if kw is not None:
                 kw.argtypes, kw.restype = [c_int], ctypes.c_char_p
@@ -326,7 +338,8 @@ _TYPED_ELSEWHERE = {"toa_bn_ws_floats", "toa_attn_bwd_ws_bytes", "toa_host_coher
                     "toa_gemm_stream_w8_swiglu_ws_bytes", "toa_gemm_stream_w8_why", "toa_kv_q8_why",
                     "toa_decode_shared_why", "toa_gemm_wide_ws_bytes", "toa_gemm_wide_swiglu_ws_bytes",
                     "toa_gemm_wide_why", "toa_gemm_wide_w8_ws_bytes", "toa_gemm_wide_w8_swiglu_ws_bytes",
-                    "toa_gemm_wide_w8_why"}
+                    "toa_gemm_wide_w8_why", "toa_gemm_skinny_w4_ws_bytes", "toa_gemm_skinny_w4_swiglu_ws_bytes",
+                    "toa_gemm_skinny_w4_why"}
 
 
 def _fn(name: str):

@@ -59,12 +59,20 @@ def _w8(x, pair, swiglu, gemm):
     launcher's own).  Refused operands -- more than 128 rows, more than 64
     under gemm="stream", or more than 16 under gemm="skinny" -- are counted
     (ops.gemm.fallbacks, warned once per shape) and the caller goes on with
-    the block's bf16 weight by `gemm`."""
+    the block's bf16 weight by `gemm`.  An MXFP4 pair (q uint8, scale uint8)
+    has the one kernel "skinny_w4" for 1 to 16 rows under every
+    weight-streaming `gemm`; more rows are counted as ``decode-fp4`` and run on
+    the bf16 weight."""
     if pair is None:
         return ""
     if gemm == "tile":
         raise ValueError('a weights snapshot needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
     rows = x.shape[0] if x.dim() == 2 else 0
+    if pair[0].dtype == torch.uint8:   # an MXFP4 pair (ops.gemm.quantize_w4): one kernel, for 1 to 16 rows
+        why = _gemm.skinny_w4_refusal(x, pair[0], pair[1], swiglu)
+        if why:
+            _gemm._fallback("decode-fp4", (x.shape[0], pair[0].shape[0], x.shape[1]), f"bf16 {gemm}", why)
+        return "" if why else "skinny_w4"
     kind = "wide" if gemm == "wide" and rows > 64 else "stream" if gemm in ("stream", "wide") and rows > 16 else "skinny"
     why = _W8_REFUSAL[kind](x, pair[0], pair[1], swiglu)
     if why:
@@ -74,8 +82,10 @@ def _w8(x, pair, swiglu, gemm):
 
 # the fp8 kernels by the rows they serve: the launcher's check, the plain form, the SwiGLU form
 _W8_REFUSAL = {"skinny": _gemm.skinny_w8_refusal, "stream": _gemm.stream_w8_refusal, "wide": _gemm.wide_w8_refusal}
-_W8_LINEAR = {"skinny": _gemm.linear_skinny_w8, "stream": _gemm.linear_stream_w8, "wide": _gemm.linear_wide_w8}
-_W8_SWIGLU = {"skinny": _gemm.swiglu_skinny_w8, "stream": _gemm.swiglu_stream_w8, "wide": _gemm.swiglu_wide_w8}
+_W8_LINEAR = {"skinny": _gemm.linear_skinny_w8, "stream": _gemm.linear_stream_w8, "wide": _gemm.linear_wide_w8,
+              "skinny_w4": _gemm.linear_skinny_w4}
+_W8_SWIGLU = {"skinny": _gemm.swiglu_skinny_w8, "stream": _gemm.swiglu_stream_w8, "wide": _gemm.swiglu_wide_w8,
+              "skinny_w4": _gemm.swiglu_skinny_w4}
 
 
 def project(x, w, gemm="tile", w8=None):
@@ -95,7 +105,9 @@ def project(x, w, gemm="tile", w8=None):
     ops.gemm.linear_stream_w8, at 65 to 128 rows under ``wide``
     ops.gemm.linear_wide_w8, and w is not read; there is no fp8 kernel above
     128 rows (above 64 under ``stream``), so those rows are counted
-    (``decode-fp8 ... -> bf16 wide``, ``-> bf16 stream``) and run on w."""
+    (``decode-fp8 ... -> bf16 wide``, ``-> bf16 stream``) and run on w.  An
+    MXFP4 pair (fmt="fp4") runs on ops.gemm.linear_skinny_w4 at 1 to 16 rows;
+    more rows are counted (``decode-fp4 ... -> bf16 <gemm>``) and run on w."""
     kind = _w8(x, w8, False, gemm)
     if kind:
         return _W8_LINEAR[kind](x, *w8, checked=True)

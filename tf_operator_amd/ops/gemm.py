@@ -899,6 +899,168 @@ def swiglu_wide_w8(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, che
     return _w8_swiglu_ref(x2, qgu, scale) if s is None else s
 
 
+# ---- 1 to 16 rows on MXFP4 weights (csrc/hip/gemm_w4.hip; the format and what the kernel takes are
+# csrc/hip/gemm_w4_shapes.h's to say).  q [N, K/2] uint8: element 2i in the low nibble of byte i, 2i+1 in the high
+# one, each e2m1; scale [N, K/32] uint8: byte X stands for 2^(X - 127), 0xff for NaN.  y = bf16(x deq^T), fp32 sums.
+W4_BLOCK = 32                    # gemm_w4_shapes.h BLOCK
+W4_E_MIN, W4_E_MAX = -100, 100   # gemm_w4_shapes.h E_MIN, E_MAX
+W4_SCALE_ALIGN = 4               # gemm_w4_shapes.h SCALE_ALIGN: bytes a row of scale starts at a multiple of
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def w4_exponents(w: torch.Tensor):
+    """(e int32 [N, K/32], finite bool [N, K/32]) of the blocks of 32 along the
+    rows of w [N, K]: a block's scale is 2^e, e the least integer with amax <=
+    6 * 2^e, from amax's exponent and mantissa (6 = 1.5 * 2^2; amax = m * 2^E,
+    0.5 <= m < 1 by frexp: e = E - 3 if m <= 0.75, else E - 2), 0 for a block
+    of zeros, clamped to -100 .. 100.  A block with a non-finite element: e =
+    0, finite False.  Plain torch on any device: the reference the quantiser
+    kernel is held against."""
+    amax = w.float().abs().view(w.shape[0], -1, W4_BLOCK).amax(2)
+    finite = torch.isfinite(amax)
+    m, E = torch.frexp(torch.where(finite, amax, torch.zeros_like(amax)))
+    e = (E - 3 + (m > 0.75).to(E.dtype)).clamp(W4_E_MIN, W4_E_MAX)
+    return torch.where((amax > 0) & finite, e, torch.zeros_like(e)).to(torch.int32), finite
+
+
+def _w4_scale_rows(N, K, device):
+    """scale [N, K/32] uint8 with rows the kernel takes: a view of rows padded to W4_SCALE_ALIGN bytes."""
+    ld = -(-(K // W4_BLOCK) // W4_SCALE_ALIGN) * W4_SCALE_ALIGN
+    return torch.zeros(N, ld, device=device, dtype=torch.uint8)[:, :K // W4_BLOCK]
+
+
+def _quantize_w4_ref(w):
+    N, K = w.shape
+    e, finite = w4_exponents(w)
+    v = torch.ldexp(w.float().view(N, -1, W4_BLOCK), -e[:, :, None]).view(N, K // 2, 2)
+    a = v.abs()
+    # round to nearest, ties to the even code; above 5 the largest code: saturation at 6, only where e met its clamp
+    code = ((a > 0.25).int() + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5)
+            + 8 * torch.signbit(v))
+    scale = _w4_scale_rows(N, K, w.device)
+    scale.copy_(torch.where(finite, e + 127, torch.full_like(e, 0xff)))
+    return (code[:, :, 0] | (code[:, :, 1] << 4)).to(torch.uint8), scale
+
+
+def quantize_w4(w: torch.Tensor):
+    """w [N, K] -> (q [N, K/2] uint8, scale [N, K/32] uint8), OCP MXFP4: e2m1
+    elements, two to a byte (the even one in the low nibble), and one e8m0
+    scale 2^e per block of 32 along a row (:func:`w4_exponents`).  An element
+    is e2m1(w 2^-e), round to nearest, ties to the even code; the product is
+    exact and at most 6, so nothing saturates unless e met its clamp, and
+    e2m1 2^e is exactly a bf16 value.  A block with a non-finite element gets
+    the scale byte 0xff: every y column that reads it is NaN.  scale is a view
+    of rows padded to 4 bytes, which is what the GEMM reads.  On the GPU:
+    toa_quant_w4 (bf16 rows with unit column stride, K a multiple of 32,
+    16-byte aligned rows; anything else raises ValueError before a launch).
+    CPU tensors take the formula in plain torch: the definition the kernel is
+    held against, bit for bit."""
+    if w.dim() != 2 or w.stride(1) != 1 or not w.is_floating_point() or w.shape[1] % W4_BLOCK or not w.shape[1]:
+        raise ValueError(f"quantize_w4: w {tuple(w.shape)} with strides {w.stride()} is not a float matrix with unit "
+                         f"column stride and K a positive multiple of {W4_BLOCK}")
+    if not _lib.use_hip(w):
+        return _quantize_w4_ref(w)
+    if w.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_w4: dtype {w.dtype}, not bf16")
+    N, K = w.shape
+    q = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    scale = _w4_scale_rows(N, K, w.device)
+    rc = _lib.call_ret("toa_quant_w4", _lib.ptr(w), w.stride(0), _lib.ptr(q), K // 2, _lib.ptr(scale), scale.stride(0),
+                       N, K, _lib.stream(w))
+    if rc == HIP_ERROR_INVALID_VALUE:
+        raise ValueError(f"quantize_w4: toa_quant_w4 takes 16-byte aligned rows, not w {tuple(w.shape)} with row "
+                         f"stride {w.stride(0)} at {w.data_ptr():#x}")
+    if rc:
+        raise RuntimeError(f"toa_quant_w4 failed with hipError {rc}")
+    return q, scale
+
+
+def dequantize_w4(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] = e2m1 2^(X - 127), exact for the quantiser's scales; NaN where X = 0xff."""
+    N, K = q.shape[0], 2 * q.shape[1]
+    code = torch.stack((q & 15, q >> 4), 2).view(N, K).long()
+    v = torch.tensor(_E2M1, device=q.device)[code & 7] * (1 - 2 * (code >> 3)).float()
+    f = torch.ldexp(torch.ones((), device=q.device), scale.int() - 127)
+    f = torch.where(scale == 0xff, torch.full_like(f, float("nan")), f)
+    return (v.view(N, -1, W4_BLOCK) * f[:, :, None]).view(N, K).to(torch.bfloat16)
+
+
+def skinny_w4_why(reason: int) -> str:
+    return _lib._fn("toa_gemm_skinny_w4_why")(reason).decode()
+
+
+def skinny_w4_refusal(x2, q, scale, swiglu: bool = False) -> str:
+    """Why (x2 [M, K], q [N, K/2] uint8, scale [N, K/32] uint8) are no operands
+    of the 1-to-16-row GEMM on MXFP4 weights, "" if they are: matrices with
+    unit column stride on one device, x2 bf16 on the GPU (any float dtype on
+    the CPU, which takes the fp32 reference), q of K/2 and scale of K/32
+    columns and as many rows as q, and a shape the launcher's check
+    (toa_gemm_skinny_w4_check) takes, in its own words."""
+    if not _lib.has("toa_gemm_skinny_w4_check"):
+        return "library built without toa_gemm_skinny_w4"
+    for t in (x2, q, scale):
+        if t.dim() != 2:
+            return f"a {t.dim()}-D tensor, not a matrix"
+        if t.stride(1) != 1:
+            return f"column stride {t.stride(1)}, not 1"
+    if q.dtype != torch.uint8 or scale.dtype != torch.uint8:
+        return f"q of dtype {q.dtype} and scale of dtype {scale.dtype}, not {torch.uint8}"
+    if x2.is_cuda and x2.dtype != torch.bfloat16:
+        return f"dtype {x2.dtype}, not bf16"
+    if not x2.device == q.device == scale.device:
+        return f"x ({x2.device}), q ({q.device}) and scale ({scale.device}) differ"
+    M, K = x2.shape
+    if 2 * q.shape[1] != K:
+        return f"K={K} columns against {2 * q.shape[1]} in the weight"
+    if tuple(scale.shape) != (q.shape[0], K // W4_BLOCK):
+        return f"scale {tuple(scale.shape)}, not one byte for each block of {W4_BLOCK} in q's {q.shape[0]} rows"
+    N = q.shape[0] // 2 if swiglu else q.shape[0]
+    # y and the workspace are the wrappers' own (contiguous, aligned): x2 stands in for them
+    r = _lib.call_ret("toa_gemm_skinny_w4_check", int(swiglu), x2.data_ptr(), q.data_ptr(), x2.data_ptr(),
+                      x2.data_ptr(), scale.data_ptr(), x2.stride(0), q.stride(0), N, scale.stride(0), q.shape[0], M, N,
+                      K)
+    return f"{skinny_w4_why(r)}: M={M} N={N} K={K}" if r else ""
+
+
+def _w4_call(name, x2, q, scale, N, swiglu, checked):
+    r = "" if checked else skinny_w4_refusal(x2, q, scale, swiglu)
+    if r:
+        raise ValueError(f"{name}: {r}")
+    if not _lib.use_hip(x2):
+        return None
+    M, K = x2.shape
+    y = torch.empty(M, N, device=x2.device, dtype=x2.dtype)
+    nbytes = int(_lib.call_ret(name + "_ws_bytes", N, K))
+    ws = _workspace(x2.device, nbytes) if nbytes > 0 else None
+    _lib.call(name, _lib.ptr(x2), x2.stride(0), _lib.ptr(q), q.stride(0), _lib.ptr(scale), scale.stride(0), _lib.ptr(y),
+              N, M, N, K, _lib.ptr(ws), _lib.stream(x2))
+    return y
+
+
+def linear_skinny_w4(x2: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """y [M, N] = x2 [M, K] deq [N, K]^T for M <= 16 on toa_gemm_skinny_w4: q
+    converted to bf16 in registers with its block's scale applied (exact),
+    fp32 accumulation, one rounding.  Operands skinny_w4_refusal names raise
+    ValueError before a launch (checked: the caller has just asked
+    skinny_w4_refusal itself, ops.decode.project; the launcher still checks
+    what it can see); CPU tensors take the fp32 GEMM on
+    :func:`dequantize_w4`."""
+    y = _w4_call("toa_gemm_skinny_w4", x2, q, scale, q.shape[0], False, checked)
+    return (x2.float() @ dequantize_w4(q, scale).float().t()).to(x2.dtype) if y is None else y
+
+
+def swiglu_skinny_w4(x2: torch.Tensor, qgu: torch.Tensor, scale: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """s [M, F] = silu(g) * u, (g | u) = x2 deq^T, qgu = gate | up [2F, K/2], for
+    M <= 16 on toa_gemm_skinny_w4_swiglu: the product is taken from the two
+    fp32 accumulators and rounded once; gu is never stored."""
+    F_ = qgu.shape[0] // 2
+    s = _w4_call("toa_gemm_skinny_w4_swiglu", x2, qgu, scale, F_, True, checked)
+    if s is None:
+        gu = x2.float() @ dequantize_w4(qgu, scale).float().t()
+        s = (torch.nn.functional.silu(gu[:, :F_]) * gu[:, F_:]).to(x2.dtype)
+    return s
+
+
 def _wgrad_reason(form: str, g, dy2, x2, split: int = 0) -> int:
     """toa_gemm_shape_check for g [N, K] (+)= dy2 [T, N]^T x2 [T, K] on the
     assembly ("wgrad_asm") or the HIP ("wgrad_hip") kernel.  g stands in for

@@ -12,7 +12,8 @@ from ..ops import sample as _sample
 from ..ops.decode import check_gemm
 
 SAMPLERS = ("torch", "device")   # what picks a token from the logits (docs/kernels.md "Sampling")
-WEIGHTS = ("bf16", "fp8")        # what the blocks' projections read (docs/kernels.md "Decoding on fp8 weights")
+# what the blocks' projections read (docs/kernels.md "Decoding on fp8 weights", "Decoding on MXFP4 weights")
+WEIGHTS = ("bf16", "fp8", "fp4")
 
 
 def check_weights(weights):
@@ -76,12 +77,15 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     prefill_chunk: Llama.prefill's chunk (None: the whole prompt at once
     through the training ops; n >= 1: n tokens at a time through the
     cache-extend kernels).
-    weights: ``bf16``, ``fp8`` or a snapshot from Llama.quantize_projections
-    (None: TOA_DECODE_WEIGHTS, default ``bf16``).  ``fp8`` quantises the
-    blocks' projections once at the start of this call -- so a trainer samples
-    from its current weights -- and the decode steps and prefill chunks of up
-    to 16 rows (``stream``: up to 64, ``wide``: up to 128) read one byte per weight
-    (Llama.decode_step weights=); it needs gemm ``skinny``, ``stream`` or ``wide``.
+    weights: ``bf16``, ``fp8``, ``fp4`` or a snapshot from
+    Llama.quantize_projections (None: TOA_DECODE_WEIGHTS, default ``bf16``).
+    ``fp8`` quantises the blocks' projections once at the start of this call
+    -- so a trainer samples from its current weights -- and the decode steps
+    and prefill chunks of up to 16 rows (``stream``: up to 64, ``wide``: up to
+    128) read one byte per weight (Llama.decode_step weights=); it needs gemm
+    ``skinny``, ``stream`` or ``wide``.  ``fp4`` is the same on MXFP4 weights:
+    up to 16 rows read four bits per weight and a scale byte per 32, more rows
+    the bf16 weights.
     kv: ``bf16`` or ``fp8`` (None: TOA_DECODE_KV, default ``bf16``): the KV
     cache in the model's dtype, or e4m3 keys and values with one power-of-two
     scale per token and KV head (Llama.new_cache(dtype=torch.float8_e4m3fn):
@@ -139,8 +143,8 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     kv = check_kv(kv)
     if samples > 1 and kv == "fp8":
         raise ValueError('samples > 1 needs kv="bf16": the shared-prompt kernels read a cache of the model\'s dtype')
-    if weights == "fp8" and gemm == "tile":
-        raise ValueError('weights="fp8" needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
+    if weights in ("fp8", "fp4") and gemm == "tile":
+        raise ValueError(f'weights="{weights}" needs gemm="skinny" or "stream": the tile GEMMs read the bf16 weights')
     lengths = [P] * groups if lengths is None else [int(n) for n in lengths]
     if len(lengths) != groups or min(lengths) < 1 or max(lengths) > P:
         raise ValueError(f"prompt lengths {lengths} outside 1 .. {P} for a batch of {groups}")
@@ -159,7 +163,8 @@ def generate(model, prompts, max_new_tokens, *, lengths=None, temperature=0.0, t
     if sampler == "torch" and not greedy:
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
-    weights = None if weights == "bf16" else model.quantize_projections() if weights == "fp8" else weights
+    if isinstance(weights, str):
+        weights = None if weights == "bf16" else model.quantize_projections(fmt=weights)
     if samples > 1:
         cache = model.new_shared_cache(groups, samples, P, capacity, device=dev)
         prompts, lengths = prompts.repeat_interleave(samples, 0), [n for n in lengths for _ in range(samples)]
